@@ -6,6 +6,28 @@ const int kBlock = 256;      // streaming kernels
 const int kBlockHeavy = 64;  // Riemann kernels: 256 VGPRs, one wave per workgroup places best (64: 61.8, 128: 62.6, 256: 71.4 ms/step)
 }
 
+// What the context knows about its states U[0], U[1] beyond their contents, so that work can be skipped: the CFL maxima a kernel
+// left in the slots d_red (the next compute_dt only reads them back), a scan accumulated piece by piece (RGPU_CORE_SCAN), ghost
+// cells the step kernel wrote itself (the next step_pre skips its fill).  A state is named by its parity, -1 names none.
+class StateRecord {
+ public:
+  void forget() { scan_ = acc_ = ghosts_ = -1; }                     // a state was written outside the step kernels
+  void scanned(int p, int n) { scan_ = p & 1; nslots_ = n; }         // U[p] was scanned into the first n slots
+  void drop_scan() { scan_ = -1; }                                   // the slots hold the maxima of no state
+  int slots(int p) const { return scan_ == (p & 1) ? nslots_ : 0; }  // how many slots hold the maxima of U[p] (0: none)
+  void arm(int p) { acc_ = p; }                                      // U[p] is scanned piece by piece into zeroed slots
+  void disarm() { acc_ = -1; }
+  bool armed(int p) const { return acc_ == (p & 1); }
+  int commit(int p) { const int n = armed(p) ? RG_DT_SLOTS : 0; acc_ = -1; if (n) scanned(p, n); return n; }   // the pieces are done
+  void ghosts_written(int p) { ghosts_ = p; }                        // the kernel that wrote U[p] wrote its ghost cells too
+  void drop_ghosts() { ghosts_ = -1; }
+  bool ghosts_valid(int p) const { return ghosts_ == p; }
+  // a device-clock batch stopped behind U[p]: the steps after it did nothing, the slots (with ghosts: the ghost cells) are still its
+  void stopped_at(int p, bool ghosts) { scan_ = p; acc_ = -1; ghosts_ = ghosts ? p : -1; }
+ private:
+  int scan_ = -1, nslots_ = 1, acc_ = -1, ghosts_ = -1;
+};
+
 struct rgpu_ctx {
   rgpu_params p;
   DevParams g;
@@ -35,11 +57,7 @@ struct rgpu_ctx {
   bool fork_ok;
   int device;           // HIP device the context was created on; every entry point makes it current
   unsigned xcd_sub;     // sub-band size (cells) of the XCD-aware workgroup order of THIS context, 0 = linear
-  int fused_dt_parity;  // parity of the state whose CFL maximum the last sweep left in d_red (-1: none)
-  int fused_dt_slots;   // how many slots of d_red hold it (1: hydro sweep; RG_DT_SLOTS: MHD update kernel)
-  int ghost_ok_parity;  // parity of the state whose ghost cells the step kernel itself left valid (2D MHD, periodic box: images written
-                        // by the fused kernel), -1: none -- the plain path then skips the ghost fill of that state at the next step's entry
-  int scan_acc_parity;  // parity of the state whose CFL maximum is being accumulated piece by piece (RGPU_CORE_SCAN), -1: none
+  StateRecord rec;      // what the slots d_red and the ghost cells hold of U[0], U[1]
   // device-side time step (hip/step_clock.h; rgpu_run_steps): records of a batch on the device / pinned host memory, and the record the
   // step being queued reads (0: the step takes its by-value dt arguments)
   enum { kClockBatch = RGPU_CLOCK_BATCH };
@@ -172,7 +190,9 @@ void fill_dev_params(const rgpu_params& p, DevParams* g) {
   // reference's single domain and keeps its ranges
   g->zlo_copy = (p.bc[4] == RGPU_BC_COPY && p.slab_rank > 0) ? 1 : 0;
   g->zhi_copy = (p.bc[5] == RGPU_BC_COPY && p.slab_rank < p.slab_count - 1) ? 1 : 0;
-  g->grav_on = 0; g->hgx = 0.0; g->hgy = 0.0; g->hgz = 0.0; g->G = 0; g->hdt = 0.0;   // per step: step_core_planes
+  // static gravity: 1 uniform vector, 2 per-cell field (rgpu_set_gravity_field); of the 2D MHD steps only implementation version 0 has it
+  g->grav_on = (p.gravityEnabled && !(p.mhdEnabled && !g->three_d && (p.implementationVersion != 0 || g->rot))) ? p.gravityEnabled : 0;
+  g->hgx = 0.0; g->hgy = 0.0; g->hgz = 0.0; g->G = 0; g->hdt = 0.0;   // G: create_common; (0.5 * dt) and (0.5 * dt) * g: per step, step_core_planes
 }
 
 // number of scratch doubles per cell for each array of the active solver family
@@ -235,10 +255,6 @@ int create_common(const rgpu_params* p, double* dU, double* dU2, void* hip_strea
   c->n_order_events = 0; c->fork_ok = false;
   c->device = -1;
   c->xcd_sub = 4096;
-  c->fused_dt_parity = -1;
-  c->fused_dt_slots = 1;
-  c->scan_acc_parity = -1;
-  c->ghost_ok_parity = -1;
   if (vr) return fail(c, vr, why);
   if (rg_device_count() < 1) return fail(c, RGPU_ENODEVICE, "no HIP device: this library has no CPU fallback (backend " RG_BACKEND_NAME ")");
   c->device = rg_current_device();
@@ -269,6 +285,7 @@ int create_common(const rgpu_params* p, double* dU, double* dU2, void* hip_strea
     c->ou->init(p->ouInitRandom, p->ouTimeScaleTurb, p->ouAmplitudeTurb, p->ouKsi);
   }
   if (p->gravityEnabled == 2 && alloc_zero(c, &c->G, c->ncell * 3)) return fail(c, RGPU_ENOMEM, "device allocation of the gravity field failed");
+  c->g.G = c->G;
   if (alloc_zero(c, &c->Q, c->ncell * sp.q) || alloc_zero(c, &c->E, c->ncell * sp.e) || alloc_zero(c, &c->T, c->ncell * sp.t) ||
       alloc_zero(c, &c->F, (size_t)c->g.fN * sp.f) || alloc_zero(c, &c->emf, (size_t)c->g.fN * sp.emf))
     return fail(c, RGPU_ENOMEM, "device allocation of the scratch arrays failed");

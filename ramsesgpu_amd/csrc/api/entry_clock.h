@@ -19,9 +19,8 @@ static bool clock_config_ok(rgpu_ctx* c) {
 }
 // ... and the state U[parity]: its CFL maxima sit in the device slots; 2D: its ghost cells are the ones its kernel wrote
 static bool clock_ready(rgpu_ctx* c, int parity) {
-  if (c->p.slab_count != 1 || !clock_config_ok(c) || c->fused_dt_parity != parity) return false;
-  if (!c->g.three_d) return c->fused_dt_slots == RG_DT_SLOTS && c->ghost_ok_parity == parity;
-  return true;
+  if (c->p.slab_count != 1 || !clock_config_ok(c) || !c->rec.slots(parity)) return false;
+  return c->g.three_d || (c->rec.slots(parity) == RG_DT_SLOTS && c->rec.ghosts_valid(parity));
 }
 static ClockConst clock_const(const rgpu_ctx* c) {
   const rgpu_params& p = c->p;
@@ -116,7 +115,7 @@ int rgpu_clock_close(rgpu_ctx* c, int nStep0, int* ran, double* t, double* dt_la
   if (ran) *ran = 0;
   if (stop) *stop = 0;
   if (queued > 0 && (rg_copy_d2h(c->h_clk, c->d_clk, (size_t)queued * sizeof(StepClock), c->stream) || rg_stream_sync(c->stream))) {
-    state_modified(c);
+    c->rec.forget();
     return RG_HIPFAIL(c, "clock_close: read-back of the records");
   }
   int r = 0;
@@ -132,9 +131,7 @@ int rgpu_clock_close(rgpu_ctx* c, int nStep0, int* ran, double* t, double* dt_la
     // the state of step nStep0 + r is the last one written, its CFL maxima are still in the slots, its ghost cells as its kernels left them
     if (stop) *stop = c->h_clk[r].stop;
     const int par = (nStep0 + r) % 2;
-    c->scan_acc_parity = -1;
-    c->fused_dt_parity = par;
-    c->ghost_ok_parity = c->g.three_d ? -1 : par;
+    c->rec.stopped_at(par, !c->g.three_d);
   }
   return RGPU_OK;
 }
@@ -166,7 +163,7 @@ int rgpu_run_steps_log(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double*
       const int n = n0 + queued;
       if (!clock_ready(c, n % 2)) rc = RGPU_EHIP;   // (cannot happen: the step before left its CFL maxima and, in 2D, its ghost cells)
       if (rc == 0) rc = (step_pre(c, n) || step_core(c, n, 0.0, 0.0) || step_post_a(c, n, 0.0, 0.0) || step_post_b(c, n)) ? RGPU_EHIP : 0;
-      if (rc == 0 && c->fused_dt_parity != (n + 1) % 2) rc = RGPU_EHIP;   // (cannot happen: same configuration, same kernels)
+      if (rc == 0 && !c->rec.slots((n + 1) % 2)) rc = RGPU_EHIP;   // (cannot happen: same configuration, same kernels)
       if (rc) { c->clk_n = queued; break; }   // the record of the step that failed to queue is not read back
     }
     // a launch that failed after `queued` complete steps were queued: those steps still run on the device -- read their records and
@@ -177,7 +174,7 @@ int rgpu_run_steps_log(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double*
     if (rc2) return rc2;
     *nStep += ran;
     done += ran;
-    if (rc) { state_modified(c); return fail(c, RGPU_EHIP, "run_steps: queueing a device-clock step: " + launch_err); }
+    if (rc) { c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps: queueing a device-clock step: " + launch_err); }
     if (ran < queued) {
       if (stop >= 2) return fail(c, RGPU_EHIP, stop == 2 ? "run_steps: the time step is not a number" : "run_steps: 1/dt is not finite");
       break;

@@ -41,7 +41,7 @@ const char* rgpu_last_error(rgpu_ctx* c) { return c ? c->err.c_str() : "null con
 
 int rgpu_upload(rgpu_ctx* c, const double* hU, int both) {
   RG_CHECK_CTX(c);
-  state_modified(c);
+  c->rec.forget();
   if (!hU || !c->U[0]) return fail(c, RGPU_EINVAL, "upload: null pointer / context without state");
   const size_t bytes = c->ncell * (size_t)c->p.nbVar * sizeof(double);
   if (rg_copy_h2d(c->U[0], hU, bytes, c->stream)) return RG_HIPFAIL(c, "upload");
@@ -140,7 +140,7 @@ int rgpu_read_cell(rgpu_ctx* c, int parity, int i, int j, int k, double* out) {
 // Periodic / copy / shearing faces rewrite ghosts with bit-identical images of interior values (or leave that face
 // alone), so the scan result stands.
 static void boundary_call_invalidates_dt(rgpu_ctx* c, int parity, int dim_lo, int dim_hi) {
-  if (c->fused_dt_parity != (parity & 1)) return;   // (a scan being accumulated piece by piece belongs to the slab driver's own schedule)
+  if (!c->rec.slots(parity)) return;   // (a scan being accumulated piece by piece belongs to the slab driver's own schedule)
   bool keeps = true;
   for (int d = dim_lo; d <= dim_hi; ++d) {
     if (d == RGPU_ZDIR && !c->g.three_d) continue;
@@ -150,12 +150,12 @@ static void boundary_call_invalidates_dt(rgpu_ctx* c, int parity, int dim_lo, in
     }
   }
   if (c->p.enableJet) keeps = false;
-  if (!keeps) c->fused_dt_parity = -1;
+  if (!keeps) c->rec.drop_scan();
 }
 
 int rgpu_invalidate_dt(rgpu_ctx* c) {
   if (!c) return RGPU_EINVAL;
-  state_modified(c);
+  c->rec.forget();
   return RGPU_OK;
 }
 
@@ -220,23 +220,16 @@ int rgpu_inv_dt_result(rgpu_ctx* c, double* invDt) {
   if (!invDt || !c->U[0]) return fail(c, RGPU_EINVAL, "inv_dt_result: null pointer / context without state");
   // slab contexts: always every slot -- the ranks all-reduce a fixed RG_DT_SLOTS values, and a rank after a full scan (slot 0 + zeros,
   // inv_dt_scan) must still see a peer's fused maxima in the other slots
-  const int nslots = (c->p.slab_count > 1) ? (int)RG_DT_SLOTS : (c->fused_dt_parity >= 0 ? c->fused_dt_slots : 1);
+  const int nslots = (c->p.slab_count > 1) ? (int)RG_DT_SLOTS : std::max(1, std::max(c->rec.slots(0), c->rec.slots(1)));
   if (inv_dt_fetch(c, invDt, nslots)) return RG_HIPFAIL(c, "inv_dt_result");
   return RGPU_OK;
 }
 int rgpu_inv_dt_fusable(rgpu_ctx* c) {
   if (!c || !c->U[0] || !c->g.three_d) return 0;
-  return (c->p.mhdEnabled ? mhd3d_scan_cond(c) : hydro3d_scan_cond(c)) ? 1 : 0;
+  return (c->p.mhdEnabled ? mhd3d_pieces_scan(c) : hydro3d_sweep_scan(c)) ? 1 : 0;
 }
-int rgpu_inv_dt_fused_active(rgpu_ctx* c, int parity) { return (c && c->U[0] && c->scan_acc_parity == (parity & 1)) ? 1 : 0; }
-int rgpu_inv_dt_fused_commit(rgpu_ctx* c, int parity) {
-  if (!c || !c->U[0]) return 0;
-  if (c->scan_acc_parity != (parity & 1)) { c->scan_acc_parity = -1; return 0; }
-  c->scan_acc_parity = -1;
-  c->fused_dt_parity = parity & 1;
-  c->fused_dt_slots = RG_DT_SLOTS;
-  return RG_DT_SLOTS;
-}
+int rgpu_inv_dt_fused_active(rgpu_ctx* c, int parity) { return (c && c->U[0] && c->rec.armed(parity)) ? 1 : 0; }
+int rgpu_inv_dt_fused_commit(rgpu_ctx* c, int parity) { return (c && c->U[0]) ? c->rec.commit(parity) : 0; }
 
 int rgpu_history_columns(rgpu_ctx* c, int parity, double* cols) {
   RG_CHECK_CTX(c);

@@ -57,7 +57,7 @@ double forcing_norm(const rgpu_params& p, const double* s, double dt) {   // Hyd
 }
 
 int add_forcing(rgpu_ctx* c, int parity, double norm) {
-  state_modified(c);
+  c->rec.forget();
   K_add_forcing k = {c->g, c->U[parity & 1], c->Frc, norm};
   return launch_planes<kBlock, 1>(c->stream, c->g, clip(c->g.gw, c->g.ksize - c->g.gw, c->g.ksize), k);
 }
@@ -65,7 +65,7 @@ int add_forcing(rgpu_ctx* c, int parity, double norm) {
 // Ornstein-Uhlenbeck forcing on U[parity]: advance the modes on the host, then one kernel over the interior planes
 int step_ou_forcing(rgpu_ctx* c, int parity, double dt) {
   if (!c->ou) return 0;
-  state_modified(c);
+  c->rec.forget();
   Phase ph(c, RGPU_T_UPDATE);
   c->ou->update(dt, c->p.cIso);
   K_ou_forcing k = {c->g, c->U[parity & 1], c->ou->m, dt, c->p.yMin, c->p.zMin, c->p.slab_rank * c->p.nz};

@@ -5,7 +5,7 @@ namespace {
 // ---- the step -------------------------------------------------------------------------------------------------
 int step_pre(rgpu_ctx* c, int nStep) {
   if (c->g.rot) return 0;
-  if (c->ghost_ok_parity == nStep % 2) return 0;   // the kernel that wrote this state filled its ghost cells too (periodic images)
+  if (c->rec.ghosts_valid(nStep % 2)) return 0;   // the kernel that wrote this state filled its ghost cells too (periodic images)
   Phase ph(c, RGPU_T_BOUNDARIES);
   double* in = c->U[nStep % 2];
   FillXY f;
@@ -87,23 +87,52 @@ int launch_planes(rg_stream_t s, const DevParams& g, PlaneRange r, const K& k) {
   return rg_launch_planes<BLOCK, MINW>(s, (unsigned)r.lo * g.sk, g.sk, (unsigned)(r.hi - r.lo), k, (unsigned)g.xcd_sub);
 }
 
-// Can the update kernels of a 3D MHD step carry the CFL scan of the new state (see mhd3d_core)?  Depends on this
-// context's boundary types: slabs of one run may answer differently (the slab driver agrees on the minimum once, at
-// rgpu_comm_create, through rgpu_inv_dt_fusable).
-bool mhd3d_scan_cond(const rgpu_ctx* c) {
-  const rgpu_params& p = c->p;
-  const DevParams& g = c->g;
-  if (g.grav_on == 2 || p.nu > 0 || p.eta > 0 || p.randomForcingEnabled || p.ouForcingEnabled) return false;
-  if (g.rot) {
-    const bool xy_ok = (p.bc[0] == RGPU_BC_PERIODIC || p.bc[0] == RGPU_BC_SHEARINGBOX) && p.bc[1] == p.bc[0];
-    auto zok = [](int b) { return b == RGPU_BC_PERIODIC || b == RGPU_BC_COPY; };
-    return xy_ok && p.bc[2] == RGPU_BC_PERIODIC && p.bc[3] == RGPU_BC_PERIODIC && zok(p.bc[4]) && zok(p.bc[5]);
+// ---- what the kernel that writes the new state carries along ---------------------------------------------------------------
+// The CFL scan of the new state rides in that kernel when nothing modifies the state afterwards (no dissipative stage, no forcing)
+// and the next compute_dt reads exactly what the kernel wrote.  One function per step family: how many slots of d_red the kernel
+// fills (0: the scan is left to compute_dt).  They depend on the context's configuration alone; slabs of one run may answer
+// differently (the slab driver agrees on the minimum once, at rgpu_comm_create, through rgpu_inv_dt_fusable).
+bool no_later_write(const rgpu_params& p, bool mhd) { return !(p.nu > 0) && !(mhd && p.eta > 0) && !p.randomForcingEnabled && !p.ouForcingEnabled; }
+bool periodic_xy(const rgpu_params& p) { return p.bc[0] == RGPU_BC_PERIODIC && p.bc[1] == RGPU_BC_PERIODIC && p.bc[2] == RGPU_BC_PERIODIC && p.bc[3] == RGPU_BC_PERIODIC; }
+// hydro 3D, the LDS-tiled sweep: whole-domain steps, and slab pieces (RGPU_CORE_SCAN) accumulating into the same slot
+int hydro3d_sweep_scan(const rgpu_ctx* c) { return no_later_write(c->p, false) && rgpu_tiled::hydro3d_sweep_covers(c->g) && c->g.grav_on != 2 ? 1 : 0; }
+// hydro 2D (fused step or flat update) and the flat 3D update (RGPU_TILED=0, per-cell gravity field): whole-domain steps
+int hydro_flat_scan(const rgpu_ctx* c) { return no_later_write(c->p, false) ? RG_DT_SLOTS : 0; }
+// 2D MHD (fused step or flat update): on the rotating path (ghosts refilled before the reference scans) with four periodic faces,
+// whose refilled high faces are bit-identical copies
+int mhd2d_scan(const rgpu_ctx* c) {
+  return c->g.grav_on != 2 && no_later_write(c->p, true) && (!c->g.rot || periodic_xy(c->p)) ? RG_DT_SLOTS : 0;
+}
+// 3D MHD slab pieces (RGPU_CORE_SCAN): the field on the three high faces keeps its CT value -- always on the plain path (the reference
+// scans before the ghosts are refilled); on the rotating path when y, z are periodic (bit-identical copies) and x is periodic or the
+// shearing box (its fill skips the first outer Bx face).  A z face shared with a neighbour slab (RGPU_BC_COPY) counts as periodic.
+int mhd3d_pieces_scan(const rgpu_ctx* c) {
+  const auto& bc = c->p.bc;
+  auto zok = [](int b) { return b == RGPU_BC_PERIODIC || b == RGPU_BC_COPY; };
+  const bool rot_ok = (bc[0] == RGPU_BC_PERIODIC || bc[0] == RGPU_BC_SHEARINGBOX) && bc[1] == bc[0] && bc[2] == RGPU_BC_PERIODIC &&
+                      bc[3] == RGPU_BC_PERIODIC && zok(bc[4]) && zok(bc[5]);
+  return c->g.grav_on != 2 && no_later_write(c->p, true) && (!c->g.rot || rot_ok) ? RG_DT_SLOTS : 0;
+}
+// 3D MHD whole domain: as the pieces, but the whole-slab step of a rotating slab leaves the scan to the driver
+int mhd3d_scan(const rgpu_ctx* c) { return c->g.rot && (c->p.bc[4] == RGPU_BC_COPY || c->p.bc[5] == RGPU_BC_COPY) ? 0 : mhd3d_pieces_scan(c); }
+// The 2D fused kernels write the ghost images of their output too when they scan it, the faces are plain and there is no jet (the
+// next step_pre skips its fill).  Hydro: Dirichlet, Neumann or periodic faces (the kernel's mask of face types, 0: no images);
+// MHD: periodic faces, not on the rotating frame.
+int hydro2d_images(const rgpu_ctx* c) {
+  if (!rgpu::options().ghost_images || !hydro_flat_scan(c) || c->p.enableJet || c->g.nx < c->g.gw || c->g.ny < c->g.gw) return 0;
+  int images = 1 << 12;
+  for (int f = 0; f < 4; ++f) {
+    const int bc = c->p.bc[f];
+    if (bc != RGPU_BC_DIRICHLET && bc != RGPU_BC_NEUMANN && bc != RGPU_BC_PERIODIC) return 0;
+    images |= bc << (2 * f);
   }
-  return true;
+  return images;
 }
-bool hydro3d_scan_cond(const rgpu_ctx* c) {
-  return !(c->p.nu > 0) && !c->p.randomForcingEnabled && !c->p.ouForcingEnabled && rgpu_tiled::hydro3d_sweep_covers(c->g) && c->g.grav_on != 2;
+bool mhd2d_images(const rgpu_ctx* c) {
+  return rgpu::options().ghost_images && !c->g.rot && mhd2d_scan(c) && !c->p.enableJet && c->g.nx >= c->g.gw && c->g.ny >= c->g.gw && periodic_xy(c->p);
 }
+// zero the slots a fused scan is about to fill -- unless a clock kernel of this step already did
+int zero_scan_slots(rgpu_ctx* c) { return c->clk_cur ? 0 : rg_memset_async(c->d_red, 0, RG_DT_SLOTS * sizeof(unsigned long long), c->stream); }
 
 // hydro: launch-time specialisation on the Riemann solver and the slope type (launchers.h); the no-gravity instantiations
 // only, everything else runs the generic kernels
@@ -125,44 +154,34 @@ int hydro_core(rgpu_ctx* c, const double* in, double* out, double dt_arg, int a,
   const double dt = st.dt;
   const double dtdx = dt / g.dx, dtdy = dt / g.dy, dtdz = dt / g.dz;
   const int ks = g.ksize;
+  const int out_par = (out == c->U[0]) ? 0 : 1;
+  const bool whole = a <= 0 && b >= ks;
   if (ND == 3) {   // LDS-tiled z-marching sweep: the whole step in one kernel (hip/tiled_hydro.h)
     Phase ph(c, RGPU_T_SWEEP);
-    // whole-domain steps whose output nothing modifies afterwards carry the CFL scan of the new state along; slab pieces
-    // (acc_piece: RGPU_CORE_UPDATE | RGPU_CORE_SCAN after a reset by the FLUXES call) accumulate into the same slot
-    const bool cond = hydro3d_scan_cond(c);
-    const bool scan = a <= 0 && b >= ks && cond && !acc_piece;
-    const bool piece = acc_piece && cond && c->scan_acc_parity == ((out == c->U[0]) ? 0 : 1);
-    if (acc_piece && !piece) c->scan_acc_parity = -1;
-    if (scan && !c->clk_cur && rg_memset_async(c->d_red, 0, RG_DT_SLOTS * sizeof(unsigned long long), c->stream)) return -1;   // (a clock kernel zeroed them)
+    // slab pieces (acc_piece: RGPU_CORE_UPDATE | RGPU_CORE_SCAN after a reset by the FLUXES call) accumulate into the same slot
+    const int n3 = hydro3d_sweep_scan(c);
+    const bool scan = whole && n3 && !acc_piece;
+    const bool piece = acc_piece && n3 && c->rec.armed(out_par);
+    if (acc_piece && !piece) c->rec.disarm();
+    if (scan && zero_scan_slots(c)) return -1;
     const int rc = rgpu_tiled::hydro3d_sweep(c->stream, g, in, out, dtdx, dtdy, dtdz, a, b, (scan || piece) ? c->d_red : 0, st.clk, a2, b2);
-    if (rc == 0 && scan) { c->fused_dt_parity = (out == c->U[0]) ? 0 : 1; c->fused_dt_slots = 1; }
+    if (rc == 0 && scan) c->rec.scanned(out_par, n3);
     if (rc <= 0) return rc;
     if (st.clk) return -1;   // the flat kernels take dt by value
-    if (acc_piece) c->scan_acc_parity = -1;   // flat kernels took over: no accumulated scan for this step
+    if (acc_piece) c->rec.disarm();   // flat kernels took over: no accumulated scan for this step
   }
-  // the CFL scan of the new state rides in the kernel that writes it when the whole domain is updated in this call and nothing
-  // modifies the state afterwards (2D: the fused step or the flat update kernel; 3D with a per-cell gravity field: the flat one)
-  const bool scan2 = a <= 0 && b >= ks && !(c->p.nu > 0) && !c->p.randomForcingEnabled && !c->p.ouForcingEnabled;
+  const int n = whole ? hydro_flat_scan(c) : 0;
   const bool folding = c->clk_cur && c->fold_mode && c->fold_pending;   // 2D batch: the clock is part of this step's kernel (ClockFold)
-  unsigned long long* slots = scan2 ? c->d_red : 0;
-  if (st.clk && !(ND == 2 && scan2)) return -1;   // a device-clock step is a fused kernel with the CFL term or nothing
-  if (scan2 && !c->clk_cur && rg_memset_async(c->d_red, 0, RG_DT_SLOTS * sizeof(unsigned long long), c->stream)) return -1;   // (the clock kernel zeroed them)
+  unsigned long long* slots = n ? c->d_red : 0;
+  if (st.clk && !(ND == 2 && n)) return -1;   // a device-clock step is a fused kernel with the CFL term or nothing
+  if (n && zero_scan_slots(c)) return -1;
   if (ND == 2) {   // LDS-tiled fused step: one kernel (hip/tiled_hydro2d.h)
     Phase ph(c, RGPU_T_SWEEP);
-    // plain faces, nothing modifying the new state after this kernel: it writes the ghost images too and the next step's fill is skipped
-    int images = 0;
-    if (rgpu::options().ghost_images && scan2 && !c->p.enableJet && g.nx >= g.gw && g.ny >= g.gw) {
-      images = 1 << 12;
-      for (int f = 0; f < 4; ++f) {
-        const int bc = c->p.bc[f];
-        if (bc != RGPU_BC_DIRICHLET && bc != RGPU_BC_NEUMANN && bc != RGPU_BC_PERIODIC) { images = 0; break; }
-        images |= bc << (2 * f);
-      }
-    }
+    const int images = hydro2d_images(c);
     const int rc = rgpu_tiled::hydro2d_step(c->stream, g, in, out, dtdx, dtdy, slots, images, folding ? 0 : st.clk, folding ? &c->fold : 0);
     if (rc == 0 && folding) c->fold_pending = false;
-    if (rc == 0 && scan2) { c->fused_dt_parity = (out == c->U[0]) ? 0 : 1; c->fused_dt_slots = RG_DT_SLOTS; }
-    if (rc == 0 && images) c->ghost_ok_parity = (out == c->U[0]) ? 0 : 1;
+    if (rc == 0 && n) c->rec.scanned(out_par, n);
+    if (rc == 0 && images) c->rec.ghosts_written(out_par);
     if (rc <= 0) return rc;
     if (st.clk) return -1;   // the flat kernels take dt by value
   }
@@ -192,7 +211,7 @@ int hydro_core(rgpu_ctx* c, const double* in, double* out, double dt_arg, int a,
     K_hydro_update<ND, NV, true> kg = {g, in, out, c->F, dtdx, dtdy, dtdz, slots};
     if (gf ? launch_planes<kBlock, 1>(c->stream, g, clip(a, b, ks), kg) : launch_planes<kBlock, 1>(c->stream, g, clip(a, b, ks), k)) return -1;
   }
-  if (scan2) { c->fused_dt_parity = (out == c->U[0]) ? 0 : 1; c->fused_dt_slots = RG_DT_SLOTS; }
+  if (n) c->rec.scanned(out_par, n);
   return 0;
 }
 
@@ -225,31 +244,26 @@ int mhd2d_core(rgpu_ctx* c, const double* in, double* out, double dt_arg) {
   const double dt = st.dt;
   const double dtdx = dt / g.dx, dtdy = dt / g.dy;
   const RotCoef rc = rot_coef(c, dt);
+  const int out_par = (out == c->U[0]) ? 0 : 1;
+  const int n = mhd2d_scan(c);
+  unsigned long long* slots = n ? c->d_red : 0;
   {
-    // LDS-tiled fused step (hip/tiled_mhd2d.h): U -> Unew in one kernel, the CFL term of the new state included under the
-    // conditions of the flat update kernel below.  Not with a Dirichlet face (its ghost fill leaves B alone, so the output's
-    // ghost cells must be copies of the input's: the flat update copies them, the fused kernel writes its own cells only).
-    const rgpu_params& p = c->p;
+    // LDS-tiled fused step (hip/tiled_mhd2d.h): U -> Unew in one kernel, the CFL term of the new state included as in the flat
+    // update kernel below.  Not with a Dirichlet face (its ghost fill leaves B alone, so the output's ghost cells must be copies of
+    // the input's: the flat update copies them, the fused kernel writes its own cells only).
     bool faces_ok = true;
-    for (int f = 0; f < 4; ++f) faces_ok = faces_ok && (p.bc[f] == RGPU_BC_PERIODIC || p.bc[f] == RGPU_BC_NEUMANN);
-    if (faces_ok && g.grav_on != 2) {
-      bool scan = !(p.nu > 0) && !(p.eta > 0) && !p.randomForcingEnabled && !p.ouForcingEnabled;
-      if (scan && g.rot) scan = p.bc[0] == RGPU_BC_PERIODIC && p.bc[1] == RGPU_BC_PERIODIC && p.bc[2] == RGPU_BC_PERIODIC && p.bc[3] == RGPU_BC_PERIODIC;
-      if (rgpu_tiled::mhd2d_step_covers(g)) {
-        if (st.clk && !scan) return -1;
-        if (scan && !c->clk_cur && rg_memset_async(c->d_red, 0, RG_DT_SLOTS * sizeof(unsigned long long), c->stream)) return -1;   // (the clock kernel zeroed them)
-        Phase ph(c, RGPU_T_SWEEP);
-        // periodic box on the plain path, nothing modifying the new state after this kernel: it writes the periodic images too and
-        // the next step's ghost fill is skipped (step_pre)
-        bool images = rgpu::options().ghost_images && !g.rot && scan && !p.enableJet && g.nx >= g.gw && g.ny >= g.gw;
-        for (int f = 0; f < 4; ++f) images = images && p.bc[f] == RGPU_BC_PERIODIC;
-        const int rct = rgpu_tiled::mhd2d_step<kSpecPlain>(c->stream, g, rc, pick_spec(g) == 2, in, out, dt, scan ? c->d_red : 0, images ? 1 : 0, st.clk);
-        if (rct < 0) return -1;
-        if (rct == 0) {
-          if (scan) { c->fused_dt_parity = (out == c->U[0]) ? 0 : 1; c->fused_dt_slots = RG_DT_SLOTS; }
-          if (images) c->ghost_ok_parity = (out == c->U[0]) ? 0 : 1;
-          return 0;
-        }
+    for (int f = 0; f < 4; ++f) faces_ok = faces_ok && (c->p.bc[f] == RGPU_BC_PERIODIC || c->p.bc[f] == RGPU_BC_NEUMANN);
+    if (faces_ok && rgpu_tiled::mhd2d_step_covers(g)) {
+      if (st.clk && !n) return -1;
+      if (n && zero_scan_slots(c)) return -1;
+      Phase ph(c, RGPU_T_SWEEP);
+      const bool images = mhd2d_images(c);
+      const int rct = rgpu_tiled::mhd2d_step<kSpecPlain>(c->stream, g, rc, pick_spec(g) == 2, in, out, dt, slots, images ? 1 : 0, st.clk);
+      if (rct < 0) return -1;
+      if (rct == 0) {
+        if (n) c->rec.scanned(out_par, n);
+        if (images) c->rec.ghosts_written(out_par);
+        return 0;
       }
     }
   }
@@ -263,21 +277,14 @@ int mhd2d_core(rgpu_ctx* c, const double* in, double* out, double dt_arg) {
     K_mhd_flux2d<true> kg = {g, c->T, c->F};
     if (gf ? rg_launch<kBlockHeavy>(c->stream, c->n32, kg) : rg_launch<kBlockHeavy>(c->stream, c->n32, k)) return -1;
   }
-  // the CFL scan of the new state rides in the update kernel under the conditions of the 3D step (mhd3d_core): nothing
-  // modifies the state afterwards, and on the rotating path (ghosts refilled before the reference scans) the refilled high
-  // faces are bit-identical periodic copies
-  const rgpu_params& p = c->p;
-  bool scan = !gf && !(p.nu > 0) && !(p.eta > 0) && !p.randomForcingEnabled && !p.ouForcingEnabled;
-  if (scan && g.rot) scan = p.bc[0] == RGPU_BC_PERIODIC && p.bc[1] == RGPU_BC_PERIODIC && p.bc[2] == RGPU_BC_PERIODIC && p.bc[3] == RGPU_BC_PERIODIC;
-  unsigned long long* slots = scan ? c->d_red : 0;
-  if (scan && !c->clk_cur && rg_memset_async(c->d_red, 0, RG_DT_SLOTS * sizeof(unsigned long long), c->stream)) return -1;
+  if (n && zero_scan_slots(c)) return -1;
   {
     Phase ph(c, RGPU_T_UPDATE);
     K_mhd_update2d<false> k = {g, rc, in, out, c->F, dt, dtdx, dtdy, slots};
     K_mhd_update2d<true> kg = {g, rc, in, out, c->F, dt, dtdx, dtdy, slots};
     if (gf ? rg_launch<kBlock>(c->stream, c->n32, kg) : rg_launch<kBlock>(c->stream, c->n32, k)) return -1;
   }
-  if (scan) { c->fused_dt_parity = (out == c->U[0]) ? 0 : 1; c->fused_dt_slots = RG_DT_SLOTS; }
+  if (n) c->rec.scanned(out_par, n);
   return 0;
 }
 
@@ -381,27 +388,20 @@ int mhd3d_core(rgpu_ctx* c, const double* in, double* out, double dt_arg, double
     const unsigned j0 = (unsigned)r.lo * g.jsize, jn = (unsigned)(r.hi - r.lo) * g.jsize;
     return rg_launch_range<kBlock>(s, j0, jn, k_ssave) || rg_launch_range<kBlock>(s, j0, jn, k_sremap);
   };
-  // The CFL scan of the new state rides in the update kernel when the whole domain is updated in one call and the
-  // next compute_dt will see exactly this state: nothing modifies it afterwards (no dissipative stage / forcing), and the
-  // field on the three high boundary faces keeps its CT value -- always true on the plain path (the reference scans
-  // before the ghosts are refilled), on the rotating path when y, z are periodic (the refilled faces are bit-identical
-  // copies) and x is periodic or the shearing box (its ghost fill skips the first outer Bx face).
-  // Slab pieces (RGPU_CORE_SCAN with the split calls): the same scan accumulated over the update launches of a step -- the
-  // slots are reset by the FLUXES call; a z face shared with a neighbour slab (RGPU_BC_COPY) counts like a periodic one: the
-  // exchanged faces are the doubles this slab's own CT update gives them.
+  // The CFL scan of the new state rides in the update kernel when the whole domain is updated in one call; slab pieces
+  // (RGPU_CORE_SCAN with the split calls) accumulate it over the update launches of a step -- the slots are reset by the FLUXES call.
   const bool acc = (what & RGPU_CORE_SCAN) != 0;
   what &= ~RGPU_CORE_SCAN;
-  const bool cond = mhd3d_scan_cond(c);
-  const int out_parity = (out == c->U[0]) ? 0 : 1;
-  bool scan = what == 0 && a <= 0 && b >= ks && cond;
-  if (scan && g.rot && (p.bc[4] == RGPU_BC_COPY || p.bc[5] == RGPU_BC_COPY)) scan = false;   // whole-slab call of a slab: the driver scans
+  const int out_par = (out == c->U[0]) ? 0 : 1;
+  const int n = (what == 0 && a <= 0 && b >= ks) ? mhd3d_scan(c) : 0;
+  const bool pieces = mhd3d_pieces_scan(c) != 0;
   if (acc && what == RGPU_CORE_FLUXES) {
-    c->scan_acc_parity = cond ? out_parity : -1;
-    if (cond && !c->clk_cur && rg_memset_async(c->d_red, 0, RG_DT_SLOTS * sizeof(unsigned long long), c->stream)) return -1;   // (a clock kernel zeroed them)
+    if (pieces) c->rec.arm(out_par); else c->rec.disarm();
+    if (pieces && zero_scan_slots(c)) return -1;
   }
-  const bool scan_piece = acc && what == RGPU_CORE_UPDATE && cond && c->scan_acc_parity == out_parity;
-  unsigned long long* slots = (scan || scan_piece) ? c->d_red : 0;
-  if (scan && !c->clk_cur && rg_memset_async(c->d_red, 0, RG_DT_SLOTS * sizeof(unsigned long long), c->stream)) return -1;
+  const bool scan_piece = acc && what == RGPU_CORE_UPDATE && pieces && c->rec.armed(out_par);
+  unsigned long long* slots = (n || scan_piece) ? c->d_red : 0;
+  if (n && zero_scan_slots(c)) return -1;
   // the update is a pure stream over F, emf and U: one thread per column and short z segment, linear workgroup order, the plane
   // k+1 entries carried in registers (mhd_update3d_column; 512^3: 8.07 -> 7.42 ms against one thread per cell)
   const int upd_seg = 3;   // planes per thread of the update's z march (512^3: 2 / 3 / 4 / 8 / 32 planes 7.49 / 7.42 / 7.50 / 7.65 / 9.0 ms)
@@ -447,7 +447,7 @@ int mhd3d_core(rgpu_ctx* c, const double* in, double* out, double dt_arg, double
     }
     if (what != RGPU_CORE_FLUXES) {
       { Phase ph(c, RGPU_T_UPDATE); if (update_planes(s, clip(a, b, ks), pair ? clip(a2, b2, ks) : PlaneRange{0, 0})) return -1; }
-      if (scan) { c->fused_dt_parity = (out == c->U[0]) ? 0 : 1; c->fused_dt_slots = RG_DT_SLOTS; }
+      if (n) c->rec.scanned(out_par, n);
     }
     return 0;
   }
@@ -484,7 +484,7 @@ int mhd3d_core(rgpu_ctx* c, const double* in, double* out, double dt_arg, double
       d_upd = kb_prev;
     }
   }
-  if (scan) { c->fused_dt_parity = (out == c->U[0]) ? 0 : 1; c->fused_dt_slots = RG_DT_SLOTS; }
+  if (n) c->rec.scanned(out_par, n);
   return 0;
 }
 
@@ -496,24 +496,19 @@ int step_core_planes(rgpu_ctx* c, int nStep, double dt, double totalTime, int a,
   bool hydro_piece = false;
   if ((what & ~RGPU_CORE_SCAN) != 0 && !splittable) {
     if ((what & ~RGPU_CORE_SCAN) == RGPU_CORE_FLUXES) {   // nothing to compute; with SCAN: reset the slot for the pieces that follow
-      c->scan_acc_parity = -1;
-      if (acc && c->g.three_d && !c->p.mhdEnabled && !(c->p.nu > 0) && !c->p.randomForcingEnabled && !c->p.ouForcingEnabled &&
-          rgpu_tiled::hydro3d_sweep_covers(c->g) && c->p.gravityEnabled != 2) {
-        if (!c->clk_cur && rg_memset_async(c->d_red, 0, RG_DT_SLOTS * sizeof(unsigned long long), c->stream)) return -1;   // (a clock kernel zeroed them)
-        c->scan_acc_parity = (nStep + 1) % 2;
+      c->rec.disarm();
+      if (acc && hydro3d_sweep_scan(c)) {   // (3D hydro only: the sweep covers nothing else)
+        if (zero_scan_slots(c)) return -1;
+        c->rec.arm((nStep + 1) % 2);
       }
       return 0;
     }
     hydro_piece = acc && c->g.three_d && !c->p.mhdEnabled;
     what = 0;
   }
-  c->fused_dt_parity = -1;   // the output array is about to change (a whole-domain hydro sweep sets it again)
-  c->ghost_ok_parity = -1;
-  // static gravity of this step: (0.5 * dt) * g, the reference's "HALF_F * dt * h_gravity"; of the 2D MHD steps only
-  // implementation version 0 has it
-  c->g.grav_on = (c->p.gravityEnabled && !(c->p.mhdEnabled && !c->g.three_d && (c->p.implementationVersion != 0 || c->g.rot))) ? 1 : 0;
-  if (c->g.grav_on && c->p.gravityEnabled == 2) c->g.grav_on = 2;   // per-cell field (rgpu_set_gravity_field)
-  c->g.G = c->G;
+  c->rec.drop_scan();   // the output array is about to change (the kernel that writes it records what it carries along)
+  c->rec.drop_ghosts();
+  // static gravity of this step (g.grav_on, fill_dev_params): (0.5 * dt) * g, the reference's "HALF_F * dt * h_gravity"
   c->g.hdt = 0.5 * dt;
   c->g.hgx = 0.5 * dt * c->p.gravity_x;
   c->g.hgy = 0.5 * dt * c->p.gravity_y;
@@ -565,19 +560,10 @@ int dissipative_nd(rgpu_ctx* c, double* U, double dt, double nu, double eta) {
   return 0;
 }
 
-// Every entry point that WRITES a state array outside the step kernels calls this: what the context remembers about that state --
-// the CFL maximum a kernel left in the device slots (fused_dt_parity), a scan being accumulated piece by piece
-// (scan_acc_parity), ghost cells the step kernel wrote itself (ghost_ok_parity) -- is void from here on.
-inline void state_modified(rgpu_ctx* c) {
-  c->fused_dt_parity = -1;
-  c->scan_acc_parity = -1;
-  c->ghost_ok_parity = -1;
-}
-
 int step_dissipative(rgpu_ctx* c, int nStep, double dt, double totalTime, bool fill_ghosts = true) {
   const double nu = c->p.nu, eta = c->p.mhdEnabled ? c->p.eta : 0.0;
   if (!(nu > 0 || eta > 0)) return 0;
-  state_modified(c);
+  c->rec.forget();
   Phase ph(c, RGPU_T_DISSIPATIVE);
   double* U = c->U[(nStep + 1) % 2];
   int rc = 0;
@@ -599,8 +585,8 @@ int step_core(rgpu_ctx* c, int nStep, double dt, double totalTime) {
 
 // max of the per-cell 1/dt over the flat index range [idx0, idx0+n) into the device slot (reset or accumulate)
 int inv_dt_scan(rgpu_ctx* c, int parity, unsigned idx0, unsigned n, bool reset) {
-  c->fused_dt_parity = -1;   // the slot is rewritten
-  c->scan_acc_parity = -1;
+  c->rec.drop_scan();   // the slots are rewritten
+  c->rec.disarm();
   Phase ph(c, RGPU_T_DT);
   const double* U = c->U[parity & 1];
   // a fresh scan owns ALL slots: the maximum goes to slot 0, slots 1 .. RG_DT_SLOTS-1 (which a fused scan of an earlier step may
@@ -637,7 +623,7 @@ int inv_dt_fetch(rgpu_ctx* c, double* invDt, int nslots = 1) {
 }
 
 int inv_dt(rgpu_ctx* c, int parity, double* invDt) {
-  if (c->fused_dt_parity == (parity & 1)) return inv_dt_fetch(c, invDt, c->fused_dt_slots);   // the kernel that wrote this state scanned it
+  if (const int n = c->rec.slots(parity)) return inv_dt_fetch(c, invDt, n);   // the kernel that wrote this state scanned it
   return inv_dt_scan(c, parity, 0, c->n32, true) || inv_dt_fetch(c, invDt);
 }
 

@@ -50,7 +50,7 @@ RG_DEVFN ImgDim images_of(int x, int n, int gw, int bc_lo, int bc_hi) {
 // images != 0 (bit 12 set, the four face types in bits 2f .. 2f+1; caller: whole-domain step, every face dirichlet / neumann /
 // periodic, no jet, nothing modifies the new state after this kernel): the interior cells also write the ghost cells the next
 // step's ghost fill (X, then Y over the full extent: corners are images of images) would copy them into -- the same doubles -- and
-// the ghost cells' own threads do not store: one writer per location, and that fill is not launched (ghost_ok_parity).
+// the ghost cells' own threads do not store: one writer per location, and that fill is not launched (StateRecord::ghosts_written).
 template <int TX, int TY, int SPEC>
 __global__ void __launch_bounds__(TX * TY) hydro2d_step_kernel(DevParams g, int nbx, const double* __restrict__ Uin, double* __restrict__ Uout,
                                                                double dtdx, double dtdy, unsigned long long* dt_slots, int images, const StepClock* clk, ClockFold fold) {

@@ -542,6 +542,93 @@ def check_public_ghost_fill_invalidates_fused_dt(lib, oracle, base, ov):
         sv.close()
 
 
+
+# ---- what a step leaves behind for the next one: the CFL scan in the device slots, the ghost images, rgpu_inv_dt_fusable ----------
+# One rgpu_godunov_unsplit per case, then: does the next compute_dt scan, does the next step_pre fill ghosts (not on the rotating
+# frame, where step_pre does nothing), and (3D) rgpu_inv_dt_fusable before and after the step.  Columns: scan -- the step's kernel
+# leaves the CFL maxima of its output (both builds); images -- the tiled 2D kernel writes the output's ghost images (None: rotating
+# frame); fusable -- (flat kernels, tiled kernels), None in 2D.
+FUSED_BOOKKEEPING = [
+    ("hydro2d-periodic", "kelvin_helmholtz_gpu_2d", "mesh.nx=24;mesh.ny=16", True, True, None),
+    ("hydro2d-dirichlet", "hydro_sod2d", "mesh.nx=20;mesh.ny=16", True, True, None),
+    ("hydro2d-jet", "jet2d_cpu", "mesh.nx=24;mesh.ny=16", True, False, None),
+    ("hydro2d-gravity", "rayleigh_taylor_gpu_2d", "mesh.nx=16;mesh.ny=24", True, True, None),
+    ("hydro2d-gravity-field", "Keplerian_disk2d", "mesh.nx=20;mesh.ny=20", True, False, None),
+    ("mhd2d-periodic", "orszag-tang", "mesh.nx=24;mesh.ny=20", True, True, None),
+    ("mhd2d-neumann", "mhd_BrioWu", "mesh.nx=24;mesh.ny=16", True, False, None),
+    ("mhd2d-dirichlet", "orszag-tang", "mesh.nx=24;mesh.ny=20;mesh.boundary_xmin=1;mesh.boundary_xmax=1;mesh.boundary_ymin=1;mesh.boundary_ymax=1", True, False, None),
+    ("mhd2d-rotating", "mhd_inertialWave_2d", "mesh.nx=16;mesh.ny=16", True, None, None),
+    ("mhd2d-eta", "orszag-tang", "mesh.nx=24;mesh.ny=20;MHD.eta=0.01", False, False, None),
+    ("hydro3d-implode", "implode3d", "mesh.nx=8;mesh.ny=8;mesh.nz=8", True, False, (0, 1)),
+    ("hydro3d-gravity", "rayleigh_taylor_gpu_3d", "mesh.nx=8;mesh.ny=8;mesh.nz=12", True, False, (0, 1)),
+    ("hydro3d-forcing", "turbulence_hydro", "mesh.nx=8;mesh.ny=8;mesh.nz=8", False, False, (0, 0)),
+    ("mhd3d-orszag-tang", "orszag-tang3d", "mesh.nx=8;mesh.ny=8;mesh.nz=8", True, False, (1, 1)),
+    ("mhd3d-mri", "mhd_mri_3d", "mesh.nx=8;mesh.ny=12;mesh.nz=8", True, None, (1, 1)),
+    ("mhd3d-mri-gravity-field", "mhd_mri_3d", "mesh.nx=6;mesh.ny=8;mesh.nz=6;gravity.static=yes", False, None, (0, 0)),
+    ("mhd3d-mri-open-z", "mhd_mri_3d", "mesh.nx=8;mesh.ny=12;mesh.nz=8;mesh.boundary_zmin=2;mesh.boundary_zmax=2", False, None, (0, 0)),
+    ("mhd3d-nu", "orszag-tang3d", "mesh.nx=8;mesh.ny=8;mesh.nz=8;hydro.nu=0.005", False, False, (0, 0)),
+]
+
+
+def _host_state(lib, sv, parity):
+    """emulation build: the "device" state is host memory, written here without telling the library"""
+    import ctypes as C
+    n = int(np.prod(sv.p.shape))
+    return np.ctypeslib.as_array((C.c_double * n).from_address(lib.lib.rgpu_device_state(sv.ctx, parity))).reshape(tuple(sv.p.shape))
+
+
+def check_fused_bookkeeping(lib, case):
+    import os
+    _, base, ov, scan, images, fusable = case
+    emu = "emulation" in lib.backend
+    tiled = not emu and os.environ.get("RGPU_TILED", "1").strip() != "0"
+    p = lib.params_from_ini(ini(base), ov)
+    U0 = lib.init_condition(ini(base), ov, p)
+    rot = bool(p.mhdEnabled) and p.Omega0 > 0
+    sv = Solver(p, lib)
+    try:
+        attach_gravity(lib, base, ov, p, sv)
+        sv.start(U0, 0)
+        before = lib.lib.rgpu_inv_dt_fusable(sv.ctx)
+        dt = sv.compute_dt(0)
+        sv.godunov_unsplit(0, dt, 0.0)
+        after = lib.lib.rgpu_inv_dt_fusable(sv.ctx)
+        gw = p.ghostWidth
+        cell = (gw, gw, gw) if p.three_d else (0, gw, gw)
+        ghost = (gw, gw, 0) if p.three_d else (0, gw, 0)
+        if emu:
+            # a fast cell in the new state: a scan sees it, a maximum left by the step's kernel does not
+            U = _host_state(lib, sv, 1)
+            saved = U[2][cell]
+            U[2][cell] = 1e4 * U[0][cell]
+            got = sv.compute_inv_dt(1)
+            assert lib.lib.rgpu_invalidate_dt(sv.ctx) == 0
+            fresh = sv.compute_inv_dt(1)
+            U[2][cell] = saved
+            assert lib.lib.rgpu_invalidate_dt(sv.ctx) == 0
+            assert fresh > sv.compute_inv_dt(1)      # (the fast cell is visible)
+            scans = got == fresh
+            fills = None
+            if not rot:
+                U[0][ghost] = -12345.0
+                sv.step_pre(1, dt, dt)
+                fills = U[0][ghost] != -12345.0
+        else:
+            sv.enable_timers(True)
+            sv.reset_timers()
+            sv.compute_inv_dt(1)
+            scans = sv.timers()["dt"] > 0.0
+            sv.reset_timers()
+            sv.step_pre(1, dt, dt)
+            fills = None if rot else sv.timers()["boundaries"] > 0.0
+            sv.enable_timers(False)
+    finally:
+        sv.close()
+    want_fills = None if rot else not (images and tiled and lib.get_option("ghost_images") != 0)
+    assert (scans, fills) == (not scan, want_fills), ("next compute_dt scans, next step_pre fills", (scans, fills), (not scan, want_fills))
+    if p.three_d:
+        assert before == after == fusable[1 if tiled else 0], ("rgpu_inv_dt_fusable before / after the first step", before, after)
+
 # ---- direct differential test of the Alfven selection in the 2D HLLD edge solver (rgpu_selftest_alfven) -------------------------
 def alfven_samples(n, seed):
     """(kept for the last few (n, seed): the four parameter sets of the selection test run on the same samples; read-only)"""

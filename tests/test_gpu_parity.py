@@ -382,6 +382,13 @@ def test_public_ghost_fill_invalidates_fused_dt(base, ov, gpu_lib, oracle):
     pc.check_public_ghost_fill_invalidates_fused_dt(gpu_lib, oracle, base, ov)
 
 
+
+@pytest.mark.parametrize("case", pc.FUSED_BOOKKEEPING, ids=[c[0] for c in pc.FUSED_BOOKKEEPING])
+def test_fused_scan_and_ghost_bookkeeping(case, gpu_lib):
+    """tiled kernels: which step leaves the CFL maxima of its output for the next compute_dt (phase timer of the scan), which leaves
+    its ghost cells for the next step_pre (phase timer of the fill), and rgpu_inv_dt_fusable the same before and after the first step"""
+    pc.check_fused_bookkeeping(gpu_lib, case)
+
 def test_orszag_tang_large_box_properties(gpu_lib):
     """the fused 2D MHD kernel at a size the oracle does not run in seconds (2048^2: 137 x 293 tiles, the periodic ghost images
     written by the kernel itself): div B stays at round-off, mass / energy / momentum are conserved to round-off in the periodic

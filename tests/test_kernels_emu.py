@@ -145,3 +145,10 @@ FUSED_FILL = [("implode3d", "mesh.nx=10;mesh.ny=8;mesh.nz=12"),                 
 @pytest.mark.parametrize("base,ov", FUSED_FILL, ids=["%s-%d" % (c[0], n) for n, c in enumerate(FUSED_FILL)])
 def test_one_launch_ghost_fill_equals_the_separate_passes(base, ov, emu_lib, oracle):
     pc.check_fused_fill(emu_lib, oracle, base, ov)
+
+
+@pytest.mark.parametrize("case", pc.FUSED_BOOKKEEPING, ids=[c[0] for c in pc.FUSED_BOOKKEEPING])
+def test_fused_scan_and_ghost_bookkeeping(case, emu_lib):
+    """flat kernels: which step leaves the CFL maxima of its output for the next compute_dt, which leaves its ghost cells for the next
+    step_pre, and rgpu_inv_dt_fusable the same before and after the first step"""
+    pc.check_fused_bookkeeping(emu_lib, case)
