@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 def lib_path(arithmetic=None):
     """in-tree location of the product library (built by __graft_entry__.build / ramsesgpu_amd/build.py).
     arithmetic: "exact" (librgpu.so: bit-identical to the reference) or "contracted" (librgpu_fast.so: FMA contraction,
-    ~1-ulp division / square root; agrees with the reference to round-off); default from $RGPU_ARITH, else exact."""
+    division within 18 ulp, square root within 1 ulp; agrees with the reference to round-off); default from $RGPU_ARITH, else exact."""
     if os.environ.get("RGPU_LIB"):   # an experiment build (scripts/)
         return os.environ["RGPU_LIB"]
     arithmetic = arithmetic or os.environ.get("RGPU_ARITH", "exact")

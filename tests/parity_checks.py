@@ -151,6 +151,321 @@ def check_single_step_random(lib, oracle, base, ov, seed=3, mach=1.5, t0=2.0):
         sv.close()
 
 
+# ---- stress states: the floors, degenerate and tied branches the smooth problems and random_state never reach ------------------------
+# Every family is seeded, admissible to the oracle (check_single_step_stress asserts its output finite) and checks on the numpy side
+# that it holds what it claims (StressStateError otherwise): a family that has gone soft fails as a generator error, not as a pass.
+STRESS_FAMILIES = ("rough", "contrast", "lowbeta", "floor", "patches")
+
+
+class StressStateError(AssertionError):
+    pass
+
+
+def stress_families(p):
+    """the families that apply to a configuration: lowbeta needs a magnetic field, and an isothermal sound speed that leaves beta
+    below 1e-3 under |B| ~ 1"""
+    return [f for f in STRESS_FAMILIES if f != "lowbeta" or (p.nbVar == 8 and 2.0 * p.cIso * p.cIso < 1e-3)]
+
+
+_MHD_BASES = ("orszag-tang", "orszag-tang3d", "mhd_BrioWu", "mhd_mri_3d", "mhd_mri_3d_stratified", "mhd_inertialWave_2d")
+
+
+def stress_cases(shapes):
+    """[(base, ov, family)] for [(base, ov, ...)]: every family that applies (stress_families, decided here from the names so that
+    collection needs no library: the tests assert that it agrees)"""
+    out = []
+    for s in shapes:
+        base, ov = s[0], s[1]
+        cs = [float(kv.split("=")[1]) for kv in ov.split(";") if kv.startswith("hydro.cIso=")]
+        cs = cs[-1] if cs else (0.001 if base.startswith("mhd_mri_3d") else 0.0)
+        for f in STRESS_FAMILIES:
+            if f != "lowbeta" or (base in _MHD_BASES and 2.0 * cs * cs < 1e-3):
+                out.append((base, ov, f))
+    return out
+
+
+def _plus1(a, axis):
+    """a[.., i + 1, ..] along axis, the last layer repeated (it only feeds the outermost ghost layer)"""
+    out = np.empty_like(a)
+    n = a.shape[axis]
+    src = [slice(None)] * a.ndim
+    dst = [slice(None)] * a.ndim
+    src[axis], dst[axis] = slice(1, n), slice(0, n - 1)
+    out[tuple(dst)] = a[tuple(src)]
+    src[axis], dst[axis] = slice(n - 1, n), slice(n - 1, n)
+    out[tuple(dst)] = a[tuple(src)]
+    return out
+
+
+def centred_field(p, B):
+    """the cell-centred field of the MHD primitives (dev_numerics.h: mhd_prim): the mean of the cell's low face and the +1 neighbour's;
+    in 2D the z neighbour counts as 0.  B: [3][k][j][i] face field"""
+    bx = 0.5 * (B[0] + _plus1(B[0], 2))
+    by = 0.5 * (B[1] + _plus1(B[1], 1))
+    bz = 0.5 * (B[2] + _plus1(B[2], 0)) if p.three_d else 0.5 * B[2]
+    return np.array([bx, by, bz])
+
+
+def _assemble(p, rho, vel, pres, B=None, emag=None):
+    """conservative state from primitives; the energy uses the centred field exactly as the primitives recover it (or emag)"""
+    nv = p.nbVar
+    U = np.zeros(p.shape)
+    U[0] = rho
+    U[2] = rho * vel[0]
+    U[3] = rho * vel[1]
+    ekin = 0.5 * rho * (vel[0] ** 2 + vel[1] ** 2)
+    if nv >= 5:
+        U[4] = rho * vel[2]
+        ekin = ekin + 0.5 * rho * vel[2] ** 2
+    if nv == 8:
+        U[5:8] = B
+        if emag is None:
+            emag = 0.5 * (centred_field(p, B) ** 2).sum(0)
+    else:
+        emag = 0.0
+    U[1] = pres / (p.gamma0 - 1.0) + ekin + emag
+    return U
+
+
+def stress_pressure(p, U):
+    """the pressure the primitives recover from U (before the floor), in the kernel's order of operations; ghosts included"""
+    r = U[0]
+    u, v = U[2] / r, U[3] / r
+    eken = 0.5 * (u * u + v * v)
+    if p.nbVar >= 5:
+        w = U[4] / r
+        eken = 0.5 * (u * u + v * v + w * w)
+    emag = 0.5 * (centred_field(p, U[5:8]) ** 2).sum(0) if p.nbVar == 8 else 0.0
+    return (p.gamma0 - 1.0) * r * ((U[1] - emag) / r - eken)
+
+
+def _interior_cells(p, a):
+    gw = p.ghostWidth
+    return a[gw:-gw, gw:-gw, gw:-gw] if p.three_d else a[:, gw:-gw, gw:-gw]
+
+
+def stress_stats(p, U):
+    """what the generator checks: floored fraction, tied fraction, low-beta fraction, density ratio (interior cells)"""
+    r = _interior_cells(p, U[0])
+    if p.cIso > 0:
+        pres = p.cIso * p.cIso * U[0]
+        pfloor = np.zeros(U[0].shape, bool)
+    else:
+        pres = stress_pressure(p, U)
+        pfloor = pres <= U[0] * p.smallp
+    floored = float(((_interior_cells(p, U[0]) <= p.smallr) | _interior_cells(p, pfloor)).mean())
+    # all 2 ndim neighbours equal in every variable: cells one layer inside the interior (their neighbours are interior cells)
+    gw = p.ghostWidth
+    axes = (1, 2, 3) if p.three_d else (2, 3)
+    tied = np.ones(U.shape[1:], bool)
+    for ax in axes:
+        tied &= (np.roll(U, 1, ax) == U).all(0) & (np.roll(U, -1, ax) == U).all(0)
+    inner = tied[gw + 1:-gw - 1, gw + 1:-gw - 1, gw + 1:-gw - 1] if p.three_d else tied[:, gw + 1:-gw - 1, gw + 1:-gw - 1]
+    if p.nbVar == 8:
+        b2 = (centred_field(p, U[5:8]) ** 2).sum(0)
+        lowbeta = float((_interior_cells(p, 2.0 * np.maximum(pres, U[0] * p.smallp) < 1e-3 * b2)).mean())
+    else:
+        lowbeta = 0.0
+    return {"floored": floored, "tied": float(inner.mean()) if inner.size else 0.0, "lowbeta": lowbeta,
+            "density_ratio": float(r.max() / r.min())}
+
+
+def stress_state(p, seed, family):
+    """a seeded state of one family (STRESS_FAMILIES), ghosts included (the caller fills them):
+      rough     random_state at Mach 3
+      contrast  rho and p log-uniform over 6 decades, |v| <= 10, |B| <= 3
+      lowbeta   (MHD) p ~ 1e-4 under |B| ~ 1: the pressure is what is left of E - ekin - emag
+      floor     ~20 % of cells at rho in {smallr / 2, smallr, 2 smallr} (pressure ~ rho, field ~ sqrt(rho): sound and Alfven speeds of
+                order 1, or they set a dt of 1e-7), ~30 % with E = ekin + emag exactly (every operand a short dyadic number: the recovered
+                pressure is exactly 0 and floored to rho smallp)
+      patches   piecewise-uniform blocks of 4 cells per direction: neighbours tie exactly (zero limited slopes); whole blocks with a velocity
+                component exactly 0 and fields that are purely normal (one component only) or without a normal component (adiabatic
+                only: the isothermal HLLD step of the reference is not finite at a zero normal field)"""
+    if family not in STRESS_FAMILIES:
+        raise ValueError(family)
+    if family == "lowbeta" and p.nbVar != 8:
+        raise ValueError("lowbeta is an MHD family")
+    rng = np.random.RandomState(1000 + 17 * seed + STRESS_FAMILIES.index(family))
+    nv, ks, js, is_ = p.shape
+    mhd = nv == 8
+    cells = (ks, js, is_)
+
+    def uni(lo, hi, n=None):
+        return rng.uniform(lo, hi, ((n,) if n else ()) + cells)
+
+    if family == "rough":
+        U = random_state(p, seed, mach=3.0)
+    elif family == "contrast":
+        rho, pres = 10.0 ** uni(-3, 3), 10.0 ** uni(-3, 3)
+        vel = uni(-1, 1, 3) * (10.0 / np.sqrt(3.0))
+        B = uni(-1, 1, 3) * (3.0 / np.sqrt(3.0)) if mhd else None
+        U = _assemble(p, rho, vel, pres, B)
+    elif family == "lowbeta":
+        b0 = rng.normal(size=3)
+        b0 /= np.sqrt((b0 ** 2).sum())
+        B = b0[:, None, None, None] * uni(0.8, 1.2) + 0.05 * uni(-1, 1, 3)
+        U = _assemble(p, uni(0.5, 2.0), uni(-1, 1, 3), 1e-4 * uni(0.5, 1.5), B)
+    elif family == "floor":
+        q = 1.0 / 16.0                                          # dyadic grid: every product and sum below is exact
+        kind = rng.rand(*cells)
+        light = kind < 0.24
+        # not in the last interior layer: its +1 face is a ghost face, which the ghost fill may take from an unscaled image
+        gw = p.ghostWidth
+        for ax in ((0, 1, 2) if p.three_d else (1, 2)):
+            idx = [slice(None)] * 3
+            idx[ax] = slice(cells[ax] - gw - 1, None)
+            light[tuple(idx)] = False
+        zero_p = (kind >= 0.24) & (kind < 0.54)
+        rho = np.where(zero_p, 2.0 ** rng.randint(-1, 2, cells), uni(0.5, 2.0))
+        rho = np.where(light, p.smallr * np.array([0.5, 1.0, 2.0])[rng.randint(0, 3, cells)], rho)
+        vel = np.round(uni(-3, 3, 3) / q) * q
+        pres = np.where(light, rho * uni(0.3, 1.0), uni(0.2, 1.2))
+        pres = np.where(zero_p, 0.0, pres)
+        B = None
+        if mhd:
+            B = np.round(uni(-0.7, 0.7, 3) / q) * q
+            # faces of the light cells (the cell's low face and the +1 neighbour's) scaled by a power of two ~ sqrt(smallr)
+            s = 2.0 ** np.round(0.5 * np.log2(p.smallr))
+            for c, ax in enumerate((2, 1, 0)):
+                if c == 2 and not p.three_d:
+                    B[c] = np.where(light, B[c] * s, B[c])
+                    continue
+                lo = np.roll(light, 1, ax)                      # the face i is the +1 face of cell i - 1
+                B[c] = np.where(light | lo, B[c] * s, B[c])
+        U = _assemble(p, rho, vel, pres, B)
+    else:   # patches
+        gw = p.ghostWidth
+        nb = [(n + 3) // 4 + 2 for n in cells]
+
+        def blocks(a):
+            """[..][bk][bj][bi] -> cells, block origin at the first interior cell"""
+            for ax, n in zip((-3, -2, -1), cells):
+                a = np.repeat(a, 4, axis=ax)
+                off = (4 - gw % 4) % 4 if (ax != -3 or p.three_d) else 0
+                a = np.take(a, range(off, off + n), axis=ax)
+            return a
+
+        bshape = tuple(nb) if p.three_d else (1, nb[1], nb[2])
+        rho = blocks(rng.uniform(0.5, 2.0, bshape))
+        pres = blocks(rng.uniform(0.2, 1.2, bshape))
+        v = rng.uniform(-2.0, 2.0, (3,) + bshape) * (rng.rand(3, *bshape) >= 0.35)
+        vel = blocks(v)
+        B = None
+        if mhd:
+            b = rng.uniform(-0.7, 0.7, (3,) + bshape)
+            mode = rng.randint(0, 5, bshape)                     # 0: all three, 1-3: only x / y / z (purely normal), 4: no x component
+            if p.cIso > 0:
+                # isothermal HLLD has no answer for a zero normal field (the reference's step is NaN there): all three components
+                mode[:] = 0
+            for c in range(3):
+                b[c] = np.where((mode >= 1) & (mode <= 3) & (mode != c + 1), 0.0, b[c])
+            b[0] = np.where(mode == 4, 0.0, b[0])
+            B = blocks(b)
+        # the block's own field in the energy: U is uniform inside a block (the last cell's recovered pressure differs, may be floored)
+        U = _assemble(p, rho, vel, pres, B, emag=None if B is None else 0.5 * (B ** 2).sum(0))
+    # ---- what the family claims ----
+    st = stress_stats(p, U)
+    want = {"floor": ("floored", 0.08 if p.cIso > 0 else 0.3), "patches": ("tied", 0.08 if p.three_d else 0.15),
+            "lowbeta": ("lowbeta", 0.5)}
+    if family in want:
+        k, lo = want[family]
+        if not st[k] >= lo:
+            raise StressStateError("stress_state(%s): %s fraction %.3f < %.2f" % (family, k, st[k], lo))
+    if family == "contrast" and not st["density_ratio"] >= 1e5:
+        raise StressStateError("stress_state(contrast): density ratio %.3g < 1e5" % st["density_ratio"])
+    if not np.isfinite(U).all():
+        raise StressStateError("stress_state(%s): non-finite values" % family)
+    return U
+
+
+_STRESS_CACHE = {}
+
+
+def stress_reference(oracle, lib, base, ov, family, seed=3, t0=2.0):
+    """(p, ghost-filled state, dt, oracle's step) for one case, with the generator's oracle-side checks: dt not below 1e-3 x the rough
+    family's on the same box, a finite step.  The last case is kept: the exact and contracted libraries run the same case in a row."""
+    key = (base, ov, family, seed, t0)
+    if key in _STRESS_CACHE:
+        return _STRESS_CACHE[key]
+    p = lib.params_from_ini(ini(base), ov)
+    attach_gravity(lib, base, ov, p, oracle=oracle)
+    dts = {}
+    for fam in ("rough", family):
+        U = stress_state(p, seed, fam)
+        oracle.make_all_boundaries(p, U, t0, 0.0)
+        dts[fam] = oracle.compute_dt(p, U)
+    if not dts[family] >= 1e-3 * dts["rough"]:
+        raise StressStateError("stress_state(%s) on %s [%s]: the oracle's dt %.3g is below 1e-3 x the rough family's %.3g"
+                               % (family, base, ov, dts[family], dts["rough"]))
+    dt = 0.3 * dts[family]
+    ref = oracle.godunov_unsplit(p, U.copy(), dt, t0)
+    if not np.isfinite(ref).all():
+        raise StressStateError("stress_state(%s) on %s [%s]: the oracle's step is not finite" % (family, base, ov))
+    _STRESS_CACHE.clear()
+    _STRESS_CACHE[key] = (p, U, dt, ref)
+    return _STRESS_CACHE[key]
+
+
+def _flux_partner_density(p, r):
+    """max |rho| over a cell and its face neighbours (the cells whose fluxes update it), not below smallr"""
+    m = np.abs(r)
+    for ax in ((0, 1, 2) if p.three_d else (1, 2)):
+        for s in (1, -1):
+            m = np.maximum(m, np.abs(np.roll(r, s, ax)))
+    return np.maximum(m, p.smallr)
+
+
+def assert_close_specific(got, ref, p, what, rho=None):
+    """the contracted library's bar on states whose density spans decades: relative L2 < L2_TOLERANCE per variable in specific form --
+    rho; momenta and energy over a density; the field over its square root -- so that dense cells cannot hide light ones.  Every value
+    finite.  Returns {variable: relative L2}.
+    The density of a cell's specific form is the largest |rho| of the oracle's among the cell and its face neighbours, not below smallr:
+    the update of a light cell sums fluxes of its neighbours, so a 1-ulp difference in the flux of a neighbour 1e6 times denser is a 1e-10
+    change of the light cell's own specific momentum.  Measured on MI355X with the cell's own |rho| instead: up to 3.6e-10 (floor family,
+    approx solver) and 1.3e-12 .. 1.7e-12 (contrast), ten cells or fewer carrying the whole error, every one a light cell beside a
+    cell 1e3 .. 1e10 times denser; with the flux partner's density the same runs give <= 4.5e-16.  A light cell among light cells is still
+    judged at its own scale.  (The oracle's own step leaves rho <= 0 in a few floored cells, hence |rho| and smallr.)  rho: that density,
+    when got / ref are the interior of arrays whose ghost cells hold the neighbours of the edge cells"""
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    assert np.isfinite(got).all(), "%s: non-finite values" % what
+    r = _flux_partner_density(p, ref[0]) if rho is None else rho
+    errs = {}
+    for v in range(p.nbVar):
+        scale = 1.0 if v == 0 else (1.0 / np.sqrt(r) if v >= 5 else 1.0 / r)
+        name = OT_VARS[v] if p.nbVar == 8 else ("density", "energy", "mx", "my", "mz")[v]
+        errs[name] = float(rel_l2(got[v] * scale, ref[v] * scale))
+    bad = {k: e for k, e in errs.items() if not e < L2_TOLERANCE}
+    assert not bad, "%s: specific-form relative L2 above %.0e: %s" % (what, L2_TOLERANCE, {k: "%.3e" % e for k, e in bad.items()})
+    return errs
+
+
+def check_single_step_stress(lib, oracle, base, ov, family, exact=True, seed=3, t0=2.0):
+    """one godunov_unsplit from a stress state (ghosts filled by the oracle, dt = 0.3 x the oracle's CFL dt); the interior compared --
+    and the whole array on the rotating path, which fills the ghosts of its output.  exact: every double equal; otherwise
+    assert_close_specific.  Returns the specific-form relative L2 per variable (exact=False) or None."""
+    p, U, dt, ref = stress_reference(oracle, lib, base, ov, family, seed, t0)
+    sv = Solver(p, lib)
+    try:
+        attach_gravity(lib, base, ov, p, sv=sv)
+        sv.upload(U, both=True)
+        sv.godunov_unsplit(0, dt, t0)
+        got = sv.getDataHost(1)
+    finally:
+        sv.close()
+    what = "%s [%s] single step on the %s stress state" % (base, ov, family)
+    whole = bool(p.mhdEnabled) and p.Omega0 > 0
+    if exact:
+        assert_same(interior(got, p), interior(ref, p), what)
+        if whole:
+            assert_same(got, ref, what + " incl. ghosts")
+        return None
+    rho = _flux_partner_density(p, ref[0])
+    errs = assert_close_specific(interior(got, p), interior(ref, p), p, what, rho=interior(rho[None], p)[0])
+    if whole:
+        assert_close_specific(got, ref, p, what + " incl. ghosts")
+    return errs
+
+
 def near_uniform_state(p, seed, eps):
     """a uniform magnetised flow + perturbations of relative size eps in every variable: with eps around 1e-12 the candidates of the
     Alfven-speed maxima of the 2D HLLD edge solver (dev_numerics.h: alfven_pick / alfven_duel) lie within, at and beyond the margins
@@ -308,11 +623,13 @@ BENCH_GEOMETRY = [
 ]
 
 
-def check_core_plane_pieces(lib, base, ov):
+def check_core_plane_pieces(lib, base, ov, state=None, oracle=None):
     """rgpu_step_core_planes over a partition of [0,ksize) (odd cuts, out of order) == rgpu_step_core; so is the split form
-    (rgpu_step_core_planes_split: the fluxes of the whole box once, then the update piece by piece -- the slab driver's order)"""
+    (rgpu_step_core_planes_split: the fluxes of the whole box once, then the update piece by piece -- the slab driver's order).
+    state: a stress_state family (STRESS_FAMILIES) instead of the initial condition; oracle: the whole call is also compared with the
+    oracle's step from the same state (dt equal, every double of the interior equal; the whole array on the rotating path)"""
     p = lib.params_from_ini(ini(base), ov)
-    U0 = lib.init_condition(ini(base), ov, p)
+    U0 = lib.init_condition(ini(base), ov, p) if state is None else stress_state(p, 3, state)
     ks = p.nz + 2 * p.ghostWidth
     cuts = [0, 1, 7, 8, ks - 15, ks]
     pieces = list(reversed(list(zip(cuts[:-1], cuts[1:]))))
@@ -322,6 +639,8 @@ def check_core_plane_pieces(lib, base, ov):
         sv.upload(U0)
         sv.make_all_boundaries(0, 0.0, 0.0)
         dt = sv.compute_dt(0)
+        if mode == "whole" and oracle is not None:
+            filled = sv.getDataHost(0)
         sv.step_pre(0, dt, 0.0)
         if mode == "whole":
             sv.step_core(0, dt, 0.0)
@@ -336,6 +655,15 @@ def check_core_plane_pieces(lib, base, ov):
         sv.step_post_b(0, dt, 0.0)
         outs.append(sv.getDataHost(1))
         sv.close()
+        if mode == "whole" and oracle is not None:
+            ref = U0.copy()
+            oracle.make_all_boundaries(p, ref, 0.0, 0.0)
+            assert_same(filled, ref, "%s [%s] ghost fill before the step" % (base, ov))
+            assert dt == oracle.compute_dt(p, ref), (dt, oracle.compute_dt(p, ref))
+            ref = oracle.godunov_unsplit(p, ref, dt, 0.0)
+            assert_same(interior(outs[0], p), interior(ref, p), "%s [%s] whole step_core vs oracle (%s)" % (base, ov, state or "initial condition"))
+            if p.mhdEnabled and p.Omega0 > 0:
+                assert_same(outs[0], ref, "%s [%s] whole step_core vs oracle incl. ghosts" % (base, ov))
     assert np.array_equal(outs[0], outs[1])
     assert np.array_equal(outs[0], outs[2])
 
@@ -628,6 +956,40 @@ def check_fused_bookkeeping(lib, case):
     assert (scans, fills) == (not scan, want_fills), ("next compute_dt scans, next step_pre fills", (scans, fills), (not scan, want_fills))
     if p.three_d:
         assert before == after == fusable[1 if tiled else 0], ("rgpu_inv_dt_fusable before / after the first step", before, after)
+
+# ---- the shared division / square root (rgpu_selftest_arith: rg_div(rg_recip), rg_sqrt; the compiler's "/" and sqrt) --------------
+def arith_operands():
+    """random operands over 2^+-400 (both signs) and edge operands: exact quotients, powers of two, near-ties, tiny / huge in range"""
+    rng = np.random.RandomState(7)
+    n = 1 << 20
+    num = (rng.rand(n) + 0.5) * np.exp2(rng.randint(-400, 400, n)) * np.where(rng.rand(n) < 0.5, -1.0, 1.0)
+    den = (rng.rand(n) + 0.5) * np.exp2(rng.randint(-400, 400, n)) * np.where(rng.rand(n) < 0.5, -1.0, 1.0)
+    edge_n = np.array([1.0, 3.0, 1.0, 2.0, 10.0, 1e-300, 1e300, 7.0, 0.1, 5e-324 * 2 ** 60, 1.0 + 2 ** -52, 9.0, 1e200, 1e-200])
+    edge_d = np.array([3.0, 1.0, 7.0, 2.0 ** 300, 0.1, 1e-10, 1e10, 7.0, 0.3, 3.0, 1.0 - 2 ** -53, 3.0, 1e-90, 1e95])
+    num[:edge_n.size], den[:edge_d.size] = edge_n, edge_d
+    return num, den
+
+
+def selftest_arith(lib, num, den):
+    """(rg_div(n, rg_recip(d)), n / d, rg_sqrt(n), sqrt(n)) on the device"""
+    import ctypes as C
+    n = num.size
+    quot, quot2, root, root2 = (np.empty(n) for _ in range(4))
+    P = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    lib.lib.rgpu_selftest_arith.restype = C.c_int
+    lib.lib.rgpu_selftest_arith.argtypes = [C.c_int] + [C.POINTER(C.c_double)] * 6
+    assert lib.lib.rgpu_selftest_arith(n, P(num), P(den), P(quot), P(quot2), P(root), P(root2)) == 0
+    return quot, quot2, root, root2
+
+
+def ulp_distance(got, want):
+    """distance in units in the last place between finite doubles (the number of representable doubles between them)"""
+    def key(x):
+        i = x.view(np.int64)
+        return np.where(i < 0, np.int64(-0x8000000000000000) - i, i)   # monotonic in the value, -0 == +0
+    with np.errstate(over="ignore"):
+        return np.abs(key(got) - key(want))
+
 
 # ---- direct differential test of the Alfven selection in the 2D HLLD edge solver (rgpu_selftest_alfven) -------------------------
 def alfven_samples(n, seed):

@@ -27,6 +27,18 @@ def test_single_step_on_random_state(base, ov, mach, emu_lib, oracle):
     pc.check_single_step_random(emu_lib, oracle, base, ov, mach=mach)
 
 
+STRESS_CASES = pc.stress_cases(pc.RANDOM_STEPS)
+
+
+@pytest.mark.parametrize("base,ov,family", STRESS_CASES, ids=["%s[%s]-%s" % c for c in STRESS_CASES])
+def test_single_step_on_stress_state(base, ov, family, emu_lib, oracle):
+    """the stress families of tests/test_stress_states.py on the small RANDOM_STEPS boxes through the flat kernels: pins the generator
+    and the flat kernels to the oracle, so that a failure of the GPU matrix points at the tiled code"""
+    p = emu_lib.params_from_ini(ini(base), ov)
+    assert family in pc.stress_families(p)
+    pc.check_single_step_stress(emu_lib, oracle, base, ov, family)
+
+
 @pytest.mark.parametrize("base,ov", pc.BOUNDARY_CASES, ids=["%s[%s]" % c for c in pc.BOUNDARY_CASES])
 def test_boundaries_and_dt(base, ov, emu_lib, oracle):
     pc.check_boundaries(emu_lib, oracle, base, ov)
@@ -37,6 +49,12 @@ def test_boundaries_and_dt(base, ov, emu_lib, oracle):
                                      ("implode3d", "mesh.nx=10;mesh.ny=10;mesh.nz=20")], ids=["mri", "implode3d"])
 def test_step_core_in_plane_pieces(base, ov, emu_lib):
     pc.check_core_plane_pieces(emu_lib, base, ov)
+
+
+@pytest.mark.parametrize("base,ov", [("mhd_mri_3d", "mesh.nx=8;mesh.ny=12;mesh.nz=26"),
+                                     ("implode3d", "mesh.nx=10;mesh.ny=10;mesh.nz=20")], ids=["mri", "implode3d"])
+def test_step_core_in_plane_pieces_on_contrast_state(base, ov, emu_lib, oracle):
+    pc.check_core_plane_pieces(emu_lib, base, ov, state="contrast", oracle=oracle)
 
 
 @pytest.mark.parametrize("base,ov,nsteps", pc.HISTORY_CASES, ids=["%s[%s]" % (b, o) for b, o, _ in pc.HISTORY_CASES])
