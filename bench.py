@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- headline metric of BASELINE.json: Mcell-updates/s of the unsplit Godunov step (fp64).
 
-    python bench.py --gpus N --steps K --warmup W [--workload mri|implode3d|orszag-tang] [--size S | --nx --ny --nz]
+    python bench.py --gpus N --steps K --warmup W [--workload mri|implode3d|orszag-tang] [--size S | --nx --ny --nz] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and no more: set up, W warm-up steps, the K timed steps, --dump-outputs if given,
+the JSON line (value, ms_per_step, config with its fingerprint).  --full adds every other figure listed below under
+"Extra objects": they take runs of their own (profiled steps, the other build of the library, CPU baselines, other workloads).
 
 A "step" is one oneStepIntegration of the hot path = compute_dt[_mhd] + godunov_unsplit incl. the ghost fill, on synthetic
 data; the state is resident in HBM when the timed region starts.  Workloads (BASELINE.json configs):
@@ -18,7 +22,20 @@ value = K * nx*ny*nz / t / 1e6 with t = max over ranks of the wall time of the K
 barrier + torch.cuda.synchronize() on both sides: the reference's own "cell updates per second"
 (MHDRunGodunov.cpp:4064-4068).
 
-Extra objects on the JSON line:
+Objects on every JSON line besides the headline figures:
+  config.arithmetic  which build of the library `value` was measured with.  Default "contracted": librgpu_fast.so, the
+                tolerance-grade build (FMA contraction, ~1-ulp division / square root), held to north_star's bar -- relative L2
+                < 1e-12 to euler_cpu -- by tests/test_contracted.py (all fixtures, the full 512^2 x 50 Orszag-Tang gate, 300-400 step
+                runs, the headline-size property checks; worst measured 2e-14).  --arith exact: librgpu.so, bit-identical.
+                value_arithmetic / metric_version say at the top level which build `value` is.
+  config.fingerprint  every N: sha256 of the dt sequence of all W + K steps + the sum mod 2^64 of the bit patterns of every interior double of
+                the final state (rgpu_state_checksum per rank, added up) -- identical for every --gpus N at the same arithmetic, box, K and W,
+                because the slab driver reproduces the single-device run bit for bit: a SCALE line can be checked against the N = 1 line.
+                value_exact / value_tolerance (--full) carry their own.
+  config.driver / rccl_ranks / ranks  which slab driver ran, what RCCL itself reports (ncclCommCount), device + PCI bus id per
+                rank.  --gpus N > 1 has NO fallback: it is the C++ RCCL driver or a non-zero exit.
+
+Extra objects on the JSON line, with --full only:
   roofline      dominant kernel of the step (by accumulated time): algorithmic bytes per launch (read U once + write U
                 once: 128 B per MHD cell update, 80 B hydro 3D) / its average duration measured
                 with HIP events on the kernel's stream, against the 8 TB/s HBM3E peak.  `traffic` comes from the
@@ -30,21 +47,12 @@ Extra objects on the JSON line:
                 workloads when the host has the memory).
   cpu_baseline_all_cores  ONE 256^3 box on all host cores: the restatement threaded over z-slabs (deterministic gather
                 update); `upper_bound_replicas` = independent 64^3 replicas of the reference binary, rates summed.
-  config.arithmetic  which build of the library `value` was measured with.  Default "contracted": librgpu_fast.so, the
-                tolerance-grade build (FMA contraction, ~1-ulp division / square root), held to north_star's bar -- relative L2
-                < 1e-12 to euler_cpu -- by tests/test_contracted.py (all fixtures, the full 512^2 x 50 Orszag-Tang gate, 300-400 step
-                runs, the headline-size property checks; worst measured 2e-14).  --arith exact: librgpu.so, bit-identical.
   value_exact   (every N, default arithmetic) the same workload, same K and W, through the bit-identical library librgpu.so (N=1: with its
                 own roofline; N>1: a second RCCL communicator after the first is destroyed).  --arith exact prints the contracted record
-                beside it as value_tolerance instead.  value_arithmetic / metric_version say which build `value` is.
+                beside it as value_tolerance instead.
   other_workloads  default headline run only: short measurements of BASELINE configs[1] (implode3d 256^3) and [2]
                 (orszag-tang 512^2) with their own roofline / cpu_baseline.
-  config.fingerprint  every N: sha256 of the dt sequence of all W + K steps + the sum mod 2^64 of the bit patterns of every interior double of
-                the final state (rgpu_state_checksum per rank, added up) -- identical for every --gpus N at the same arithmetic, box, K and W,
-                because the slab driver reproduces the single-device run bit for bit: a SCALE line can be checked against the N = 1 line.
-                value_exact / value_tolerance carry their own.
-  config.driver / rccl_ranks / ranks  which slab driver ran, what RCCL itself reports (ncclCommCount), device + PCI bus id per
-                rank.  --gpus N > 1 has NO fallback: it is the C++ RCCL driver or a non-zero exit.
+  ranks[].phase_ms  N>1: each rank's phase times of a step (HIP events around every launch, the same profiled steps as roofline).
 """
 import argparse
 import json
@@ -545,8 +553,9 @@ def roofline_of(wname, w, arith, step_bytes, elapsed, steps, prof):
     return roof, step
 
 
-def single_gpu_record(wname, dims, arith, steps, warmup, ctl, dump=None):
-    """one workload on ONE GPU through librgpu.so (exact) or librgpu_fast.so (contracted): value, ms/step, rooflines.
+def single_gpu_record(wname, dims, arith, steps, warmup, ctl, dump=None, profile=True):
+    """one workload on ONE GPU through librgpu.so (exact) or librgpu_fast.so (contracted): value, ms/step and, with profile,
+    the rooflines (phase_profile: steps of their own after the timed ones).
     dump: directory for what the K timed steps computed (write_dump), taken before the profiling steps run"""
     from ramsesgpu_amd.solver import Library, Solver, lib_path
     w = WORKLOADS[wname]
@@ -567,13 +576,14 @@ def single_gpu_record(wname, dims, arith, steps, warmup, ctl, dump=None):
     fingerprint = fingerprint_record(dts, [run.state_checksum(run.nStep % 2)])
     if dump:
         write_dump(dump, [dump_values(run, run.nStep % 2, nz, 0)], (int(p.nbVar), nz, ny, nx), dts[-steps:])
-    prof = phase_profile(run.oneStepIntegration, run, ctl, steps)
+    prof = phase_profile(run.oneStepIntegration, run, ctl, steps) if profile else None
     run.close()
     cells = float(nx) * ny * nz
-    roof, roof_step = roofline_of(wname, w, arith, w["bytes"] * cells, elapsed, steps, prof)
-    return {"value": steps * cells / elapsed / 1e6, "unit": "Mcell-updates/s", "ms_per_step": elapsed / steps * 1e3, "steps": steps, "warmup": warmup,
-            "roofline": roof, "roofline_step": roof_step, "library": os.path.basename(L.path), "arithmetic": arith, "parity": PARITY[arith],
-            "fingerprint": fingerprint}
+    rec = {"value": steps * cells / elapsed / 1e6, "unit": "Mcell-updates/s", "ms_per_step": elapsed / steps * 1e3, "steps": steps, "warmup": warmup}
+    if prof is not None:
+        rec["roofline"], rec["roofline_step"] = roofline_of(wname, w, arith, w["bytes"] * cells, elapsed, steps, prof)
+    rec.update({"library": os.path.basename(L.path), "arithmetic": arith, "parity": PARITY[arith], "fingerprint": fingerprint})
+    return rec
 
 
 def slab_driver_run(arith, ini, ov, rank, world, ctl):
@@ -630,6 +640,9 @@ def main():
     ap.add_argument("--nx", type=int, default=0)
     ap.add_argument("--ny", type=int, default=0)
     ap.add_argument("--nz", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (module docstring): rooflines from profiled steps, the other build "
+                         "of the library, CPU baselines, other workloads; the --no-* options below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--arith", choices=["exact", "contracted"], default=os.environ.get("RGPU_ARITH", "contracted"),
                     help="contracted (default): librgpu_fast.so, the tolerance-grade build gated at north_star's relative L2 < 1e-12; "
@@ -699,7 +712,7 @@ def main():
             elapsed = timed_steps(run.oneStepIntegration, run, ctl, args.steps, args.warmup)
             print(json.dumps({"ms_per_step": elapsed / args.steps * 1e3}))
             return
-        rec = single_gpu_record(args.workload, (nx, ny, nz), args.arith, args.steps, args.warmup, ctl, dump=args.dump_outputs)
+        rec = single_gpu_record(args.workload, (nx, ny, nz), args.arith, args.steps, args.warmup, ctl, dump=args.dump_outputs, profile=args.full)
         driver, rccl_ranks = "single device: %s, no communicator" % rec["library"], None
         ranks = [dict(device_facts(torch, local_rank), rank=0)]
     else:
@@ -770,15 +783,17 @@ def main():
             ctl.close()
             return
         clocked_steps = srun.clocked_steps() if slab_batch is not None else None
-        prof = phase_profile(step, timers_src, ctl, args.steps)
-        roof, roof_step = roofline_of(args.workload, w, args.arith, w["bytes"] * cells_local, elapsed, args.steps, prof)
-        rec = {"value": args.steps * cells_global / elapsed / 1e6, "ms_per_step": elapsed / args.steps * 1e3, "roofline": roof, "roofline_step": roof_step,
-               "fingerprint": fingerprint}
-        if info is not None and not args.no_second and os.environ.get("RGPU_BENCH_SECOND_ARITH", "1") != "0":
+        rec = {"value": args.steps * cells_global / elapsed / 1e6, "ms_per_step": elapsed / args.steps * 1e3, "fingerprint": fingerprint}
+        prof = None
+        if args.full:
+            prof = phase_profile(step, timers_src, ctl, args.steps)
+            rec["roofline"], rec["roofline_step"] = roofline_of(args.workload, w, args.arith, w["bytes"] * cells_local, elapsed, args.steps, prof)
+        if info is not None:
+            srun.close()      # the driver's communicator: destroyed on every rank before a second one is created, or the run ends
+        if args.full and info is not None and not args.no_second and os.environ.get("RGPU_BENCH_SECOND_ARITH", "1") != "0":
             # the same slabs, same K and W, through the OTHER build of the library (a second RCCL communicator, after the first is
             # destroyed): `value` stays comparable round over round whichever build is the headline
             other = "exact" if args.arith == "contracted" else "contracted"
-            srun.close()
             srun2, info2, err2 = slab_driver_run(other, ini, ov, rank, world, ctl)
             if srun2 is None:
                 rec["second"] = (other, {"value": None, "error": repr(err2) if err2 is not None else "another rank failed"})
@@ -797,9 +812,10 @@ def main():
             mine.update(rccl_version=info.get("rccl_version"))
             if xchg is not None:
                 mine.update(last_halo_exchange=xchg)
-        # this rank's phase times of a step (hipEvents on its compute stream around every launch, 5 steps): on a multi-GPU run they show
-        # whether the traffic on the links slows the fp64-bound sweep of a rank down, rank by rank
-        mine.update(phase_ms={k: v / prof[0] * 1e3 for k, v in prof[1].items() if v > 0})
+        if prof is not None:
+            # this rank's phase times of a step (hipEvents on its compute stream around every launch, 5 steps): on a multi-GPU run they show
+            # whether the traffic on the links slows the fp64-bound sweep of a rank down, rank by rank
+            mine.update(phase_ms={k: v / prof[0] * 1e3 for k, v in prof[1].items() if v > 0})
         ranks = ctl.gather(mine)
         rccl_ranks = info["ranks"] if info is not None else None
         if info is not None:   # every rank must have seen the same communicator size, and one device each
@@ -815,7 +831,7 @@ def main():
         out = {
             "metric": "Mcell-updates/s", "value": rec["value"], "unit": "Mcell-updates/s",
             # which build of the library `value` is: since round 3 the tolerance-grade one by default (metric_version 2; rounds 1-2
-            # quoted the bit-identical library -- compare those with value_exact, which rides beside `value` at every N)
+            # quoted the bit-identical library -- compare those with value_exact, which --full puts beside `value` at every N)
             "value_arithmetic": args.arith, "metric_version": 2,
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": rec["ms_per_step"],
@@ -835,8 +851,13 @@ def main():
                                       "the device" % (clocked_steps, args.steps + args.warmup) if clocked_steps is not None else "K calls of oneStepIntegration")),
                        "parity": PARITY[args.arith],
                        "fingerprint": rec.get("fingerprint")},
-            "roofline": rec["roofline"], "roofline_step": rec["roofline_step"],
         }
+        if not args.full:
+            print(json.dumps(out))
+            ctl.close()
+            return
+        # --full: everything beside the headline, each measured in runs of its own
+        out.update(roofline=rec["roofline"], roofline_step=rec["roofline_step"])
         if world > 1 and rec.get("second"):
             out["value_exact" if rec["second"][0] == "exact" else "value_tolerance"] = rec["second"][1]
         if world == 1 and not args.no_second:

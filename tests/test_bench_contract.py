@@ -1,5 +1,6 @@
-"""bench.py's contract on the GPU box at toy sizes: one JSON line with the driver's keys plus `roofline` and (N=1)
-`cpu_baseline`, for every workload; the N>1 launch line of the driver (torch.distributed.run, one rank per GPU) exercised
+"""bench.py's contract on the GPU box at toy sizes: a plain run prints one JSON line with the driver's keys and nothing it
+would have to measure separately; --full adds `roofline`, the other build of the library and (N=1) `cpu_baseline`, for every
+workload; the N>1 launch line of the driver (torch.distributed.run, one rank per GPU) exercised
 with two ranks sharing the one GPU of the box: (i) through the explicitly selected test harness (RGPU_BENCH_DRIVER=python over gloo),
 (ii) through the default C++ RCCL driver, which must FAIL CLEANLY there (RCCL refuses two ranks on one device; there is no
 fallback), (iii) with only one device visible, where rank 1 must say so.  The C++ RCCL driver itself is covered by
@@ -10,6 +11,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -29,7 +31,7 @@ def last_json(text):
                                   ["--workload", "implode3d", "--size", "48"],
                                   ["--workload", "orszag-tang", "--size", "64"]], ids=["mri", "implode3d", "orszag-tang"])
 def test_bench_line_single_gpu(args, gpu_lib):
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + args,
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"] + args,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     d = last_json(res.stdout)
@@ -56,8 +58,35 @@ def test_bench_line_single_gpu(args, gpu_lib):
     assert ("pmc_note" in r) == (r["traffic"] is None), r.get("pmc_note")
 
 
+FULL_ONLY = {"roofline", "roofline_step", "value_exact", "value_tolerance", "cpu_baseline", "cpu_baseline_all_cores", "other_workloads"}
+
+
+def test_plain_bench_line_is_the_headline_of_the_full_one(gpu_lib, tmp_path):
+    """without --full the line carries the headline and its config and nothing that takes runs of its own; it times and dumps
+    what the --full line times and dumps: the same fingerprint, the same arrays bit for bit"""
+    box = ["--workload", "mri", "--nx", "32", "--ny", "48", "--nz", "32", "--steps", "3", "--warmup", "1"]
+    lines, dumps = {}, {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-second-arith"])):
+        dumps[name] = str(tmp_path / name)
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + box + extra + ["--dump-outputs", dumps[name]],
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines[name] = last_json(res.stdout)
+    d, f = lines["plain"], lines["full"]
+    assert (KEYS - {"roofline"}) <= set(d) and not (FULL_ONLY & set(d)), sorted(d)
+    assert "roofline" in f and "roofline_step" in f
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "value_arithmetic", "metric_version"):
+        assert d[k] == f[k], k
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / (32 * 48 * 32 * 1e-3) - 1.0) < 1e-9     # Mcell-updates/s x ms per step
+    assert d["config"]["fingerprint"] == f["config"]["fingerprint"]
+    assert all("phase_ms" not in r for r in d["config"]["ranks"])
+    for fn in ("state.npy", "dt.npy"):
+        a, b = np.load(os.path.join(dumps["plain"], fn)), np.load(os.path.join(dumps["full"], fn))
+        assert a.dtype == b.dtype == np.float64 and a.shape == b.shape and np.array_equal(a, b), fn
+
+
 def test_bench_line_exact_on_request(gpu_lib):
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--arith", "exact",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--arith", "exact",
                           "--workload", "mri", "--nx", "32", "--ny", "48", "--nz", "32"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -92,12 +121,12 @@ def test_bench_fingerprint_of_two_ranks_equals_the_single_device_line(gpu_lib, g
     state checksum) as the N = 1 line of the same box, steps and warmup, for both arithmetics: what makes the driver's SCALE lines checkable"""
     from test_comm_device import build_dev_comm
     build_dev_comm("exact"); build_dev_comm("contracted")
-    two = launch_two_ranks(dict(RGPU_BENCH_ONE_DEVICE="1", RGPU_BENCH_DRIVER="staged-test"))
+    two = launch_two_ranks(dict(RGPU_BENCH_ONE_DEVICE="1", RGPU_BENCH_DRIVER="staged-test"), ["--full"])
     assert two.returncode == 0, two.stderr[-3000:]
     d2 = last_json(two.stdout)
     assert "TEST TRANSPORT" in d2["config"]["driver"] and d2["n_gpus"] == 2 and "took their time step from the device" in d2["config"]["time_loop"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--nx", "32", "--ny", "48", "--nz", "32",
-                          "--no-cpu-baseline", "--no-other-workloads"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-other-workloads"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=600)
     assert one.returncode == 0, one.stderr[-3000:]
     d1 = last_json(one.stdout)
     for key in ("dt_sha256", "state_sum_u64", "steps"):
