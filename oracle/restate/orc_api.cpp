@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include <new>
 #include <vector>
 
 #include "orc_common.h"
@@ -209,6 +210,51 @@ int orc_godunov_unsplit(const rgpu_params* p, double* Uold, double* Unew, double
   if (!p->mhdEnabled) hydro_step(c, Uold, Unew, dt);
   else if (!c.three_d) mhd_step_2d(c, Uold, Unew, dt);
   else mhd_step_3d(c, Uold, Unew, dt, totalTime);
+  return 0;
+}
+
+// godunov_unsplit of a z window of a larger 3D box.  A cell's new value depends only on the planes within ghostWidth of it, so
+// the step of the whole box can be checked window by window.  p describes the window: nz = its w planes, zMin / zMax moved to
+// them, nz_global left at the box's value (a window of one plane is still a 3D step).  Uold holds the window's planes with
+// ghostWidth planes of the box on each side, ghosts of the box filled.  The same step as orc_godunov_unsplit, except that every
+// ghost fill of the step (the input's on the plain path, the output's on the rotating one) leaves the z ghost planes as they are:
+// Unew's interior planes, with their x and y ghost columns, are those of the whole box's step; its z ghost planes are not.
+// nthreads > 1: mhd_step_3d_mt where its scope allows (the same doubles).  Its work arrays are kept for the next window of the
+// same geometry, as orc_run_mt keeps them from step to step, until orc_zwindow_release().  Not for the dissipative stage and the
+// forcings, which refill ghosts or sum over the whole box, nor for the per-cell gravity field.
+namespace {
+struct WindowWork { int isize, jsize, ksize; MtWork* w; };
+WindowWork& window_work() { static WindowWork ww = {0, 0, 0, 0}; return ww; }
+}  // namespace
+
+void orc_zwindow_release() {
+  WindowWork& ww = window_work();
+  delete ww.w;
+  ww.w = 0;
+  ww.isize = ww.jsize = ww.ksize = 0;
+}
+
+int orc_godunov_unsplit_zwindow(const rgpu_params* p, double* Uold, double* Unew, double dt, double totalTime, int nthreads) {
+  const int rc = check_scope(p);
+  if (rc) return rc;
+  if (p->nz_global == 1 || p->nu > 0 || p->eta > 0 || p->randomForcingEnabled || p->ouForcingEnabled || p->gravityEnabled == 2)
+    return RGPU_EUNSUPPORTED;
+  Ctx c(*p);
+  c.keep_z_ghosts = true;
+  ou_forget();
+  if (!p->mhdEnabled) {
+    hydro_step(c, Uold, Unew, dt);
+  } else if (nthreads > 1 && !p->gravityEnabled && p->slope_type != 3) {
+    WindowWork& ww = window_work();
+    if (!ww.w || ww.isize != c.isize || ww.jsize != c.jsize || ww.ksize != c.ksize) {
+      orc_zwindow_release();
+      try { ww.w = new MtWork(c, nthreads); } catch (const std::bad_alloc&) { return RGPU_ENOMEM; }
+      ww.isize = c.isize; ww.jsize = c.jsize; ww.ksize = c.ksize;
+    }
+    mhd_step_3d_mt(c, *ww.w, Uold, Unew, dt, totalTime, nthreads);
+  } else {
+    mhd_step_3d(c, Uold, Unew, dt, totalTime);
+  }
   return 0;
 }
 

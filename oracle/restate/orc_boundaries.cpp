@@ -279,12 +279,12 @@ void make_all_boundaries(const Ctx& c, double* U, double totalTime, double dt) {
   if (c.p.shearingBoxEnabled && c.three_d) {
     make_boundaries(c, U, RGPU_YDIR);
     make_boundaries_shear(c, U, totalTime, dt);
-    make_boundaries(c, U, RGPU_ZDIR);
+    if (!c.keep_z_ghosts) make_boundaries(c, U, RGPU_ZDIR);
     make_boundaries(c, U, RGPU_YDIR);
   } else {
     make_boundaries(c, U, RGPU_XDIR);
     make_boundaries(c, U, RGPU_YDIR);
-    if (c.three_d) make_boundaries(c, U, RGPU_ZDIR);
+    if (c.three_d && !c.keep_z_ghosts) make_boundaries(c, U, RGPU_ZDIR);
   }
 }
 

@@ -51,6 +51,9 @@ struct Ctx {
   // h_randomForcing of the "turbulence" problem (orc_set_forcing_field)
   const double* Frc = forcing_field();
   static const double*& forcing_field() { static const double* f = 0; return f; }
+  // a z window of a larger box (orc_godunov_unsplit_zwindow): its z ghost planes are planes of that box, given by the caller,
+  // and make_all_boundaries leaves them as they are
+  bool keep_z_ghosts = false;
 };
 
 // random forcing at the end of a 3D step (HydroRunBase.cpp:1201-1312, 1397-1428)

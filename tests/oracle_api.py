@@ -80,6 +80,22 @@ class Oracle:
         assert rc == 0, rc
         return Unew
 
+    def godunov_unsplit_zwindow(self, p, Uold, dt, totalTime=0.0, nthreads=1):
+        """orc_godunov_unsplit_zwindow: one step of a z window (parity_checks.zwindow), its z ghost planes kept as given; returns Unew,
+        whose interior planes with their x / y ghost columns are those of the whole box's step.  nthreads > 1: the threaded 3D MHD
+        step where its scope allows; its work arrays stay allocated for the next window until release_zwindow()"""
+        Unew = np.empty_like(Uold)
+        f = self.lib.orc_godunov_unsplit_zwindow
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(RgpuParams), C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int]
+        rc = f(C.byref(p), self._arr(Uold), self._arr(Unew), dt, totalTime, int(nthreads))
+        assert rc == 0, rc
+        return Unew
+
+    def release_zwindow(self):
+        self.lib.orc_zwindow_release.restype = None
+        self.lib.orc_zwindow_release()
+
     def run_mt(self, p, U0, nsteps, nthreads, tEnd=1e300):
         """orc_run with the 3D MHD step threaded over z-slabs (the all-cores CPU baseline); same results as run()"""
         U = np.array(U0, dtype=np.float64, order="C", copy=True)

@@ -1127,3 +1127,288 @@ def check_fused_fill(lib, oracle, base, ov, seed=5, t0=3.7, dt=0.9):
         assert np.array_equal(got[:, gw:ks - gw], ref[:, gw:ks - gw])
     finally:
         sv.close()
+
+
+# ---- 4. a step of any size against the oracle, z window by z window ----------------------------------------------------------
+# A cell's new value depends only on the planes within ghostWidth of it.  So one step of a box too large for a single oracle call
+# is checked in z windows: each window is the window's planes plus ghostWidth planes of the box on each side, cut from the state
+# the step starts from, and orc_godunov_unsplit_zwindow steps it without refilling those z ghost planes.  Stitched together, the
+# windows are the whole-box step, every double (tests/test_zwindow_oracle.py).
+
+def zwindow(p, U, k0, w):
+    """(params, state) of the z window of interior planes [k0, k0 + w) of the ghost-inclusive 3D state U: a copy of p with nz = w and
+    zMin / zMax moved by k0 dz (nz_global stays the box's, so that a window of one plane is still a 3D step), and planes
+    k0 .. k0 + w + 2 gw of U with all of x and y"""
+    assert p.three_d and 0 <= k0 and w >= 1 and k0 + w <= p.nz, (k0, w, p.nz)
+    q = type(p).from_buffer_copy(p)
+    q.nz = w
+    q.zMin = p.zMin + k0 * p.dz
+    q.zMax = p.zMin + (k0 + w) * p.dz
+    return q, np.ascontiguousarray(U[:, k0:k0 + w + 2 * p.ghostWidth])
+
+
+def window_threads(oracle, q):
+    """threads of one window's oracle step: Oracle._mt_threads (up to 16, the threaded 3D MHD step's scope), 1 outside it"""
+    return max(1, oracle._mt_threads(q))
+
+
+def step_in_windows(oracle, p, U, dt, t, widths, nthreads=None):
+    """yields (k0, w, Unew of the window) for the windows of `widths` (a partition of [0, nz)), one after another: the oracle's
+    global state is not proven thread-safe.  nthreads None: window_threads per window"""
+    assert sum(widths) == p.nz and min(widths) >= 1, (widths, p.nz)
+    k0 = 0
+    try:
+        for w in widths:
+            q, Uw = zwindow(p, U, k0, w)
+            nt = window_threads(oracle, q) if nthreads is None else nthreads
+            out = oracle.godunov_unsplit_zwindow(q, Uw, dt, t, nt)
+            del Uw
+            yield k0, w, out
+            k0 += w
+    finally:
+        oracle.release_zwindow()
+
+
+WINDOW_SCRATCH = 24e9   # bytes of host scratch for one window's threaded oracle step (MtWork + the window's copies)
+
+
+def window_widths(p, scratch=WINDOW_SCRATCH):
+    """a partition of [0, nz) into near-equal windows whose oracle step stays within `scratch` bytes: MtWork's 182 doubles per cell
+    plus the window's input and output, over w + 2 gw planes"""
+    plane = (p.nx + 2 * p.ghostWidth) * (p.ny + 2 * p.ghostWidth)
+    per_cell = 8 * (182 + 2 * p.nbVar)
+    wmax = max(1, int(scratch // (per_cell * plane)) - 2 * p.ghostWidth)
+    n = -(-p.nz // wmax)
+    return [p.nz * (i + 1) // n - p.nz * i // n for i in range(n)]
+
+
+def _mirror_tile_grid_plan(nbx, nby, span, slots, min_planes, fill):
+    """tile_grid_plan of hip/tiled_hydro.h (one range, no RGPU_ZSEG): (nseg, ipx, full, tail)"""
+    tiles = nbx * nby
+    best_n, best_tail, best = 1, 1, 1e300
+    nmax = 1 if span // min_planes < 1 else min(span // min_planes, 64)
+    for n in range(1, nmax + 1):
+        items = tiles * n
+        ipx = (items + 7) // 8
+        full = (ipx // slots) * slots
+        rem = ipx - full
+        ln = span / n
+        tail = 1
+        if rem > 0:
+            tail = max(1, min(slots // rem, int(ln / min_planes)))
+        t = (full // slots) * (ln + fill) + ((ln / tail + fill) * ((rem * tail + slots - 1) // slots) if rem > 0 else 0.0)
+        if t < best * 0.995:
+            best, best_n, best_tail = t, n, tail
+    nseg = max(1, min(best_n, span))
+    ipx = (tiles * nseg + 7) // 8
+    full = (ipx // slots) * slots
+    return nseg, ipx, full, (best_tail if ipx - full > 0 else 1)
+
+
+def _segment_starts(nbx, nby, za, span, slots, min_planes, fill):
+    """the first plane of every z segment and last-round sub-segment of one launch (tile_item of hip/tiled_hydro.h)"""
+    nseg, ipx, full, tail = _mirror_tile_grid_plan(nbx, nby, span, slots, min_planes, fill)
+    tiles = nbx * nby
+    starts = set()
+    for xcd in range(8):
+        for item in range(xcd * ipx, min((xcd + 1) * ipx, tiles * nseg)):
+            seg = item // tiles
+            a0 = za + span * seg // nseg
+            b0 = za + span * (seg + 1) // nseg
+            nsub = tail if item - xcd * ipx >= full else 1
+            starts.update(a0 + (b0 - a0) * s // nsub for s in range(nsub))
+    return nseg, tail, sorted(starts)
+
+
+def sweep_plan_facts(p):
+    """{launch: (segments, last-round split, [first plane of each segment, ghost-inclusive])} of one whole-box step: the tiled 3D MHD
+    sweep (MhMain and, without a periodic x image, MhLastX; hip/tiled_mhd.h launch_mhd3d_sweep) and the 3-plane update, or the tiled 3D
+    hydro sweep (launch_hydro3d_sweep), at the default options"""
+    gw, isz, jsz, ks = p.ghostWidth, p.nx + 2 * p.ghostWidth, p.ny + 2 * p.ghostWidth, p.nz + 2 * p.ghostWidth
+    out = {}
+    if not p.mhdEnabled:
+        nbx, nby = (isz - 1 + 13) // 14, (jsz - 1 + 13) // 14
+        nseg, tail, st = _segment_starts(nbx, nby, gw, ks - 2 * gw, 64, 12, 2)
+        out["hydro3d_sweep"] = (nseg, tail, st)
+        return out
+    rot = p.Omega0 > 0
+    periodic = 3                                             # RGPU_BC_PERIODIC, include/rgpu.h
+    per = [p.bc[2 * d] == periodic and p.bc[2 * d + 1] == periodic for d in range(2)]
+    copy_x = per[0] and not rot and p.nx % 16 == 0 and p.nx >= 16
+    copy_y = per[1] and p.ny % 8 == 0 and p.ny >= 8
+    nbx = (isz - 2 * gw + 1 + 15) // 16 - (1 if copy_x else 0)
+    nby = (jsz - 2 * gw + 1 + 7) // 8 - (1 if copy_y else 0)
+    lastx = not copy_x and p.nx % 16 == 0 and nbx >= 2
+    if lastx:
+        nbx -= 1
+    span = ks - 2 * gw + 1                                   # the Riemann planes gw .. ksize - gw
+    out["mhd3d_sweep MhMain"] = _segment_starts(nbx, nby, gw, span, 32, 8, 2)
+    if lastx:
+        out["mhd3d_sweep MhLastX"] = _segment_starts(1, (jsz - 2 * gw + (0 if copy_y else 1) + 31) // 32, gw, span, 32, 8, 2)
+    out["mhd3d update"] = (-(-ks // 3), 1, list(range(0, ks, 3)))
+    return out
+
+
+def offset_crossing_planes(p):
+    """[(array, what, component, plane)] of the device layout (api/ctx.h fill_dev_params): the planes (ghost-inclusive) where an
+    element index of U, F or emf crosses 2^31, and where its byte offset crosses each power of two from 2^32 up"""
+    gw, isz, jsz, ks = p.ghostWidth, p.nx + 2 * p.ghostWidth, p.ny + 2 * p.ghostWidth, p.nz + 2 * p.ghostWidth
+    ncell, sk = isz * jsz * ks, isz * jsz
+    arrays = [("U", p.nbVar, ncell, 0, sk)]
+    if p.mhdEnabled:
+        fsj = (isz + 15) // 16 * 16
+        foff = (16 - gw % 16) % 16
+        fsk = fsj * jsz
+        fN = (fsk * ks + foff + 15) & ~15
+        arrays += [("F", 15, fN, foff, fsk), ("emf", 3, fN, foff, fsk)]
+    out = []
+    for name, ncomp, pitch, off, kstride in arrays:
+        total = ncomp * pitch
+        lines = [("2^31 elements", 2 ** 31)] + [("2^%d bytes" % b, 2 ** (b - 3)) for b in range(32, 64) if 2 ** (b - 3) < total]
+        for what, e in lines:
+            if e >= total:
+                continue
+            v, r = divmod(e, pitch)
+            k = min(max((r - off) // kstride, 0), ks - 1)
+            out.append((name, what, v, k))
+    return out
+
+
+def _first_diff(got, ref, k_first, interior_xy, gw):
+    """(v, k, j, i) of the first differing double, ghost-inclusive indices of the box"""
+    v, k, j, i = (int(x[0]) for x in np.nonzero(got != ref))
+    return (v, k + k_first, j + (gw if interior_xy else 0), i + (gw if interior_xy else 0))
+
+
+def check_step_in_windows(lib, oracle, base, ov, K, exact, widths=None):
+    """one step of a box of any size against the oracle, window by window: the step after K steps of the bench's path.
+      A: start(U0, 0) + run_steps(K) (time step on the device, fused CFL scan): U_K with its ghosts, t_K and the last dt.
+      B: a fresh context from the same U0, run_steps(K + 1) in one call: U_{K+1} and dt_{K+1}.  One context open at a time.
+      dt_{K+1} == the oracle's compute_dt of U_K as downloaded (contracted: relative difference < 1e-12).
+      U_K's ghosts: rotating path, equal to the oracle's make_all_boundaries of U_K with step K's own arguments (the device's end-of-step
+      fill, shear remap included); plain path, filled by the oracle as the device step does at its start.
+      Windows (window_widths, or `widths`) tile [0, nz); each is stepped by the oracle with dt_{K+1}, t_K.  Compared: the window's planes
+      over all of x and y (rotating path: with the x / y ghost columns).  exact: every double; otherwise the specific-form relative L2
+      per variable over the whole box < L2_TOLERANCE.
+      Every offset-crossing plane (offset_crossing_planes) and every segment start of the sweep launches (sweep_plan_facts) lies inside
+      a compared window.  Returns a dict of facts (also printed)."""
+    import resource
+    import time
+    t_start = time.time()
+    p = lib.params_from_ini(ini(base), ov)
+    assert p.three_d
+    gw, nz = p.ghostWidth, p.nz
+    rot = bool(p.mhdEnabled) and p.Omega0 > 0
+    what = "%s [%s], %s library, step %d" % (base, ov, lib.arithmetic, K + 1)
+    U0 = lib.init_condition(ini(base), ov, p)
+    sv = Solver(p, lib)
+    try:
+        sv.start(U0, 0)
+        assert sv.run_steps(K) == K
+        dts_a, t_K = list(sv.dt_log), sv.totalTime
+        UK = sv.getDataHost()
+    finally:
+        sv.close()
+    sv = Solver(p, lib)
+    try:
+        sv.start(U0, 0)
+        del U0
+        assert sv.run_steps(K + 1) == K + 1
+        dts_b = list(sv.dt_log)
+        UK1 = sv.getDataHost()
+    finally:
+        sv.close()
+    t_gpu = time.time() - t_start
+    assert dts_b[:K] == dts_a, (what, dts_a, dts_b)
+    t = 0.0
+    for d in dts_a[:-1]:
+        t += d                                               # the oracle's loop: t at the start of step K
+    t_prev = t
+    t += dts_a[-1]
+    assert t == t_K, (what, t, t_K)
+    dt1 = dts_b[K]
+    dt_ref = oracle.compute_dt(p, UK)
+    if exact:
+        assert dt1 == dt_ref, "%s: dt %r, the oracle's on U_K %r" % (what, dt1, dt_ref)
+    else:
+        assert abs(dt1 / dt_ref - 1.0) < 1e-12, "%s: dt %r, the oracle's on U_K %r" % (what, dt1, dt_ref)
+    # ghosts of U_K
+    if rot:
+        regions = [(slice(None), slice(0, gw)), (slice(None), slice(-gw, None)),
+                   (slice(None), slice(gw, -gw), slice(0, gw)), (slice(None), slice(gw, -gw), slice(-gw, None)),
+                   (slice(None), slice(gw, -gw), slice(gw, -gw), slice(0, gw)), (slice(None), slice(gw, -gw), slice(gw, -gw), slice(-gw, None))]
+        dev = [UK[r].copy() for r in regions]
+        oracle.make_all_boundaries(p, UK, t_prev, dts_a[-1])
+        for r, g in zip(regions, dev):
+            ref = UK[r]
+            if exact:
+                nbad = int((g != ref).sum())
+                assert nbad == 0, "%s: %d of %d ghost doubles of U_K differ from the oracle's fill %r" % (what, nbad, ref.size, r)
+            else:
+                assert_close_specific(g, ref, p, what + ": ghosts of U_K %r" % (r,), rho=np.maximum(np.abs(ref[0]), p.smallr))
+        del dev
+    else:
+        oracle.make_all_boundaries(p, UK, 0.0, 0.0)
+    # windows
+    widths = window_widths(p) if widths is None else widths
+    t_orc = time.time()
+    num = np.zeros(p.nbVar)
+    den = np.zeros(p.nbVar)
+    worst = (-1.0, None)
+    nbad_total, first = 0, None
+    for k0, w, out in step_in_windows(oracle, p, UK, dt1, t_K, widths):
+        got = UK1[:, gw + k0:gw + k0 + w]
+        ref = out[:, gw:gw + w]
+        xy = (slice(None), slice(None)) if rot else (slice(gw, -gw), slice(gw, -gw))
+        got, ref = got[(slice(None), slice(None)) + xy], ref[(slice(None), slice(None)) + xy]
+        assert np.isfinite(got).all(), "%s: non-finite values in planes %d .. %d" % (what, k0, k0 + w - 1)
+        if exact:
+            ne = got != ref
+            nb = int(ne.sum())
+            if nb and first is None:
+                first = _first_diff(got, ref, gw + k0, not rot, gw)
+            nbad_total += nb
+        else:
+            r = _flux_partner_density(p, out[0])[(slice(gw, gw + w),) + xy]
+            wl2 = 0.0
+            for v in range(p.nbVar):
+                s = 1.0 if v == 0 else (1.0 / np.sqrt(r) if v >= 5 else 1.0 / r)
+                d = (got[v] - ref[v]) * s
+                a = ref[v] * s
+                dn, dd = float((d * d).sum()), float((a * a).sum())
+                num[v] += dn
+                den[v] += dd
+                wl2 = max(wl2, np.sqrt(dn / dd) if dd > 0 else np.sqrt(dn))
+            if wl2 > worst[0]:
+                worst = (wl2, (k0, w))
+        del out, got, ref
+    t_orc = time.time() - t_orc
+    names = OT_VARS if p.nbVar == 8 else ("density", "energy", "mx", "my", "mz")
+    facts = {"case": what, "windows": widths, "gpu_s": round(t_gpu, 1), "oracle_s": round(t_orc, 1), "dt": dt1}
+    if exact:
+        assert nbad_total == 0, "%s: %d of %d compared doubles differ from the oracle; first at (v, k, j, i) = %r" % (
+            what, nbad_total, p.nbVar * nz * (UK1.shape[2] if rot else p.ny) * (UK1.shape[3] if rot else p.nx), first)
+    else:
+        errs = {names[v]: float(np.sqrt(num[v] / den[v])) if den[v] > 0 else float(np.sqrt(num[v])) for v in range(p.nbVar)}
+        facts["rel_l2_specific"] = errs
+        facts["worst_window"] = {"planes": worst[1], "rel_l2": worst[0]}
+        bad = {k: e for k, e in errs.items() if not e < L2_TOLERANCE}
+        assert not bad, "%s: specific-form relative L2 above %.0e: %s" % (what, L2_TOLERANCE, bad)
+    # the planes that matter at this size lie inside compared windows
+    starts = np.cumsum([0] + list(widths[:-1]))
+    covered = lambda k: any(s <= k - gw < s + w for s, w in zip(starts, widths))   # noqa: E731
+    nearest = lambda k: min(max(k, gw), gw + nz - 1)                               # a ghost plane: the interior plane that reads it
+    cross = offset_crossing_planes(p)
+    plan = sweep_plan_facts(p)
+    for a, line, v, k in cross:
+        assert covered(nearest(k)), (what, a, line, v, k)
+    for launch, (nseg, tail, st) in plan.items():
+        for k in st:
+            assert covered(nearest(k)), (what, launch, k)
+    facts["offset_crossings"] = ["%s %s: component %d, plane %d" % c for c in cross]
+    facts["segments"] = {k: {"segments": v[0], "last_round_split": v[1], "starts": v[2] if len(v[2]) <= 40 else v[2][:20] + ["..."] + v[2][-5:]}
+                         for k, v in plan.items()}
+    facts["wall_s"] = round(time.time() - t_start, 1)
+    facts["peak_rss_gb"] = round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1e6, 1)   # of the process so far
+    print("step in windows:", facts)
+    return facts

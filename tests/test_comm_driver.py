@@ -326,7 +326,7 @@ def test_config5_rank_geometry_through_the_rccl_driver(schedule, tmp_path):
     205 MB sent per exchange on the halo stream, asserted) for 4 steps of the overlapped and of the boundary-first schedule (the
     default at this slab thickness): (i) every double and every dt equal to the
     single-device run of the same box, (ii) div B at round-off and mass conserved to round-off (size-independent
-    properties: the oracle cannot run this size in seconds), (iii) RCCL itself reports 1 rank on the device the context uses."""
+    properties; the single-device step of the whole config-5 box is compared with the oracle in tests/test_fullsize_windows.py), (iii) RCCL itself reports 1 rank on the device the context uses."""
     code = r'''
 import os, sys
 import numpy as np
@@ -373,8 +373,9 @@ print("OK")
 @pytest.mark.parametrize("arith", ["exact", "contracted"])
 def test_config5_whole_box_on_one_gpu_properties(arith):
     """BASELINE config 5, the WHOLE box: 512 x 1024 x 512 MRI (2.7e8 cells, 75 GB at 34 doubles per cell) on one MI355X through
-    the product's slab driver (rgpu_comm, RCCL ring of one rank, overlapped schedule), 3 steps, both arithmetics.  The oracle
-    cannot run this size, so size-independent properties: div B at round-off, mass conserved to round-off (shearing-box remap
+    the product's slab driver (rgpu_comm, RCCL ring of one rank, overlapped schedule), 3 steps, both arithmetics.  Size-independent
+    properties (the single-device context's step at this size is compared with the oracle, every cell, in
+    tests/test_fullsize_windows.py): div B at round-off, mass conserved to round-off (shearing-box remap
     included), finite fields, a decreasing-or-equal CFL time step sequence of sane magnitude.  What remains untested of config 5
     is only the N > 1 RCCL exchange itself (no multi-GPU box is available to the builder; the driver's SCALE run covers it)."""
     code = r"""

@@ -102,15 +102,17 @@ def test_orszag_tang_gate_full_size(gpu_lib, oracle):
 
 
 def test_mri_headline_size_properties(gpu_lib):
-    """BASELINE config: data/mhd_mri_3d.ini scaled to 512^3 (the bench workload).  The oracle cannot run this
-    size in seconds, so size-independent properties are checked: constrained transport keeps div B at round-off,
-    the shearing box conserves mass to round-off (the remapped x-border fluxes cancel), fields stay finite."""
+    """BASELINE config: data/mhd_mri_3d.ini scaled to 512^3 (the bench workload).  Size-independent properties: constrained
+    transport keeps div B at round-off, the shearing box conserves mass to round-off (the remapped x-border fluxes cancel), fields
+    stay finite.  They hold for any consistently aliased flux or emf; tests/test_fullsize_windows.py compares a step at this size
+    with the oracle, every cell."""
     pc.mri_headline_size_properties(gpu_lib)
 
 
 def test_implode_bench_size_properties(gpu_lib):
     """BASELINE config: data/implode3d.ini at 256^3 with HLLC.  Reflecting walls: mass and energy are conserved to
-    round-off; the initial condition is symmetric under any permutation of (x,y,z) and so must the solution be."""
+    round-off; the initial condition is symmetric under any permutation of (x,y,z) and so must the solution be.  The oracle
+    comparison of a step at this size, every cell: tests/test_fullsize_windows.py."""
     pc.implode_bench_size_properties(gpu_lib)
 
 

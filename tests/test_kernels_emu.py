@@ -170,3 +170,23 @@ def test_fused_scan_and_ghost_bookkeeping(case, emu_lib):
     """flat kernels: which step leaves the CFL maxima of its output for the next compute_dt, which leaves its ghost cells for the next
     step_pre, and rgpu_inv_dt_fusable the same before and after the first step"""
     pc.check_fused_bookkeeping(emu_lib, case)
+
+
+WINDOW_CASES = [
+    ("mhd_mri_3d", "mesh.nx=16;mesh.ny=16;mesh.nz=14", 2),
+    ("orszag-tang3d", "mesh.nx=10;mesh.ny=12;mesh.nz=11", 2),
+    ("implode3d", "mesh.nx=10;mesh.ny=10;mesh.nz=12;hydro.riemannSolver=hllc", 2),
+]
+
+
+@pytest.mark.parametrize("base,ov,K", WINDOW_CASES, ids=["%s[%s]" % (b, o) for b, o, _ in WINDOW_CASES])
+def test_step_in_windows(base, ov, K, emu_lib, oracle):
+    """the full-size check of tests/test_fullsize_windows.py (parity_checks.check_step_in_windows) on small boxes, with uneven
+    windows: the harness itself runs on every CPU run"""
+    p = emu_lib.params_from_ini(ini(base), ov)
+    widths = [1, 2, 5, p.nz - 8]
+    facts = pc.check_step_in_windows(emu_lib, oracle, base, ov, K, exact=True, widths=widths)
+    assert facts["windows"] == widths
+    # the contracted library's bar, on a library whose doubles are equal: every error 0
+    facts = pc.check_step_in_windows(emu_lib, oracle, base, ov, K, exact=False, widths=widths[::-1])
+    assert set(facts["rel_l2_specific"].values()) == {0.0}, facts["rel_l2_specific"]
