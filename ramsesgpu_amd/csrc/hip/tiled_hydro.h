@@ -20,8 +20,9 @@
 // (Reference idiom: the shared-memory tiles of godunov_unsplit.cuh:1829-1988, 3212-3488 -- z-marching with the
 // flux gathered through shared memory; this is the gfx950 counterpart: wave64, 160 KB LDS, register z-pipeline.)
 //
-// Arithmetic: exactly the expressions of kernels_hydro.h (hydro_trace_cell / hydro_face_state / hydro_update_cell)
-// on the same operands in the same order, hence the same bits as the flat kernels and as the reference.
+// Arithmetic: the cell functions of kernels_hydro.h (hydro_half_slope, hydro_trace_advance, hydro_face_grid, hydro_face_flux,
+// hydro_apply_flux, hydro_gravity_source, hydro_cfl_term), the ones the flat kernels call: this kernel loads, stores, synchronises
+// and sequences, and computes nothing of its own.  Hence the same bits as the flat kernels and as the reference.
 #pragma once
 #include <cstdlib>
 
@@ -49,12 +50,29 @@ struct K_copy_cells {
   }
 };
 
-template <int TX, int TY>
+// LDS of a hydro tile (the 3D sweep: of plane kk; the fused 2D step, tiled_hydro2d.h: of the whole step)
+template <int TX, int TY, int NV>
 struct HydroTile {
-  double q[5][TY + 2][TX + 2];   // primitives of plane kk: tile + ring
-  double qm[2][5][TY][TX];       // qm_x, qm_y: state at the HIGH x / y face of each cell (grid frame, floors applied)
-  double f[2][5][TY][TX];        // flux through the LOW x / y face of each cell (face-normal frame)
+  double q[NV][TY + 2][TX + 2];   // primitives: tile + ring
+  double qm[2][NV][TY][TX];       // state at the HIGH x / y face of each cell (grid frame, floors and gravity predictor applied)
+  double f[2][NV][TY][TX];        // flux through the LOW x / y face of each cell (face-normal frame)
 };
+// Thread tiles overlap by one cell per side; thread t = (ti, tj) sits on cell (i, j).
+// ring cell of thread t < 2 TX + 2 TY in tile coordinates: the one-cell frame around the tile, corners excluded (no stencil reads them)
+template <int TX, int TY>
+RG_DEVFN void tile_ring_cell(int t, int& rti, int& rtj) {
+  if (t < TX) { rti = t; rtj = -1; }
+  else if (t < 2 * TX) { rti = t - TX; rtj = TY; }
+  else if (t < 2 * TX + TY) { rti = -1; rtj = t - 2 * TX; }
+  else { rti = TX; rtj = t - 2 * TX - TY; }
+}
+// cells a thread writes: the inner threads of the tile, plus array row / column 0 (never inner cells)
+template <int TX, int TY>
+RG_DEVFN bool tile_owns(bool ina, int ti, int tj, int i, int j) {
+  return ina && ((ti >= 1 && ti < TX - 1) || i == 0) && ((tj >= 1 && tj < TY - 1) || j == 0);
+}
+// cells the step updates (x-y part): everything but the ghost frame
+RG_DEVFN bool tile_inner(const DevParams& g, int i, int j) { return i >= g.gw && i < g.isize - g.gw && j >= g.gw && j < g.jsize - g.gw; }
 
 // map the flat block index to (tile x, tile y, z segment) so that each XCD (block b runs on XCD b % 8) owns a
 // contiguous run of tiles -- x fastest, then y, then z segment: overlapping tile edges are then re-read from that
@@ -136,7 +154,7 @@ inline void tile_grid_plan(TileGrid& tg, int span, int slots, int min_planes, in
 }
 
 // dslot != 0: the CFL scan of the NEW state rides along -- every updated cell contributes sum_d (c + |v_d|) / delta_d
-// (hydro_invdt_cell) to a 64-bit atomicMax on *dslot, so that the next compute_dt needs no pass over U (all values are
+// (hydro_cfl_term) to a 64-bit atomicMax on *dslot, so that the next compute_dt needs no pass over U (all values are
 // >= 0: the bit pattern orders like an unsigned integer; max is order independent, hence the same double as the scan)
 template <int TX, int TY, int SPEC, int MINW = 1>
 __global__ void __launch_bounds__(TX * TY, MINW) hydro3d_sweep_kernel(DevParams g, TileGrid tg, const double* __restrict__ Uin,
@@ -151,7 +169,7 @@ __global__ void __launch_bounds__(TX * TY, MINW) hydro3d_sweep_kernel(DevParams 
   constexpr int NT = TX * TY;
   constexpr int RING = 2 * TX + 2 * TY;
   static_assert(RING <= NT, "ring cells are handled by the first RING threads");
-  __shared__ HydroTile<TX, TY> L;
+  __shared__ HydroTile<TX, TY, NV> L;
 
   const TileItem item = tile_item(tg, (int)blockIdx.x, za, zb);   // this workgroup's tile and its planes [sa, sb) of [za, zb)
   if (!item.valid) return;   // whole workgroup leaves: no barrier is skipped
@@ -164,23 +182,17 @@ __global__ void __launch_bounds__(TX * TY, MINW) hydro3d_sweep_kernel(DevParams 
   const size_t N = g.ncell;
   const unsigned sk = g.sk;
   const unsigned idx2 = ina ? (unsigned)i + (unsigned)j * g.sj : 0u;
-  const int gw = g.gw;
-  // cells this thread writes: the inner threads of the tile, plus array row / column 0 (never inside an inner range)
-  const bool own = ina && ((ti >= 1 && ti < TX - 1) || i == 0) && ((tj >= 1 && tj < TY - 1) || j == 0);
-  const bool inner2d = i >= gw && i < g.isize - gw && j >= gw && j < g.jsize - gw;
+  const bool own = tile_owns<TX, TY>(ina, ti, tj, i, j);
+  const bool inner2d = tile_inner(g, i, j);
 
-  // ring cell of this thread (threads 0 .. RING-1): the one-cell frame around the tile, corners excluded
-  int rti, rtj;
-  if (t < TX) { rti = t; rtj = -1; }
-  else if (t < 2 * TX) { rti = t - TX; rtj = TY; }
-  else if (t < 2 * TX + TY) { rti = -1; rtj = t - 2 * TX; }
-  else { rti = TX; rtj = t - 2 * TX - TY; }
+  int rti, rtj;   // ring cell of this thread (threads 0 .. RING-1)
+  tile_ring_cell<TX, TY>(t, rti, rtj);
   const int ri = bx * (TX - 2) + rti, rj = by * (TY - 2) + rtj;
   const bool ring = t < RING && ri >= 0 && ri < g.isize && rj >= 0 && rj < g.jsize;
   const unsigned ridx2 = ring ? (unsigned)ri + (unsigned)rj * g.sj : 0u;
 
   const double st = g.slope_type;
-  const double gamma = g.gamma0;
+  const bool grav = g.grav_on;   // uniform static gravity (the per-cell field runs the flat kernels)
 
   double qA[NV], qB[NV], qC[NV];    // primitives of planes kk-1, kk, kk+1 of this column
   double uB[NV], uC[NV], uN[NV];    // conservative state of planes kk, kk+1, kk+2
@@ -241,101 +253,54 @@ __global__ void __launch_bounds__(TX * TY, MINW) hydro3d_sweep_kernel(DevParams 
       for (int v = 0; v < NV; ++v) urn[v] = Uin[ridx2 + (size_t)(kk + 1) * sk + v * N];
     }
 
-    // ---- B: slopes and trace of cell (i,j,kk)  (hydro_trace_cell) ----
-    double q[NV], h[3][NV];
+    // ---- B: slopes and trace of cell (i,j,kk); its high x / y face states -> LDS ----
+    double h[3][NV], tq[NV], qm[3][NV], qp[3][NV];   // half slopes, advanced state, states at the high / low face along x, y, z
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-      q[v] = qB[v];
       const double nb[3][2] = {{L.q[v][tj + 1][ti], L.q[v][tj + 1][ti + 2]}, {L.q[v][tj][ti + 1], L.q[v][tj + 2][ti + 1]}, {qA[v], qC[v]}};
 #pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        double s;
-        if (st == 0) s = 0.0;
-        else if (st == 1) s = minmod_half_slope(nb[d][0], q[v], nb[d][1]);
-        else s = tvd_half_slope(st, nb[d][0], q[v], nb[d][1]);
-        h[d][v] = s;
-      }
+      for (int d = 0; d < 3; ++d) h[d][v] = hydro_half_slope<3>(st, nb[d][0], qB[v], nb[d][1]);
     }
-    double qpx[NV], qpy[NV], qpz[NV], qmz_new[NV];
-    {
-      double r = q[ID], p = q[IP], u = q[IU], v = q[IV], w = q[IW];
-      const double drx = h[0][ID], dpx = h[0][IP], dux = h[0][IU], dvx = h[0][IV], dwx = h[0][IW];
-      const double dry = h[1][ID], dpy = h[1][IP], duy = h[1][IU], dvy = h[1][IV], dwy = h[1][IW];
-      const double drz = h[2][ID], dpz = h[2][IP], duz = h[2][IU], dvz = h[2][IV], dwz = h[2][IW];
-      const rg_recip_t inv_r = rg_recip(r);
-      const double sr0 = (-u * drx - dux * r) * dtdx + (-v * dry - dvy * r) * dtdy + (-w * drz - dwz * r) * dtdz;
-      const double su0 = (-u * dux - rg_div(dpx, inv_r)) * dtdx + (-v * duy) * dtdy + (-w * duz) * dtdz;
-      const double sv0 = (-u * dvx) * dtdx + (-v * dvy - rg_div(dpy, inv_r)) * dtdy + (-w * dvz) * dtdz;
-      const double sw0 = (-u * dwx) * dtdx + (-v * dwy) * dtdy + (-w * dwz - rg_div(dpz, inv_r)) * dtdz;
-      const double sp0 = (-u * dpx - dux * gamma * p) * dtdx + (-v * dpy - dvy * gamma * p) * dtdy + (-w * dpz - dwz * gamma * p) * dtdz;
-      double tq[NV];
-      tq[ID] = r + sr0; tq[IU] = u + su0; tq[IV] = v + sv0; tq[IW] = w + sw0; tq[IP] = p + sp0;
-      // face states with the floors of trace.h:388-389 (hydro_face_state), grid frame
-      double qmx[NV], qmy[NV];
+    hydro_trace_advance<3, NV>(g, qB, h, dtdx, dtdy, dtdz, tq);
 #pragma unroll
-      for (int n = 0; n < NV; ++n) {
-        qmx[n] = tq[n] + h[0][n]; qpx[n] = tq[n] - h[0][n];
-        qmy[n] = tq[n] + h[1][n]; qpy[n] = tq[n] - h[1][n];
-        qmz_new[n] = tq[n] + h[2][n]; qpz[n] = tq[n] - h[2][n];
-      }
-#define RG_FLOOR(a) a[ID] = fmax(g.smallr, a[ID]); a[IP] = fmax(g.smallp * a[ID], a[IP])
-      RG_FLOOR(qmx); RG_FLOOR(qpx); RG_FLOOR(qmy); RG_FLOOR(qpy); RG_FLOOR(qmz_new); RG_FLOOR(qpz);
-#undef RG_FLOOR
-      if (g.grav_on) {   // uniform static gravity: predictor on the traced states, after the floors (hydro_face_state)
-#define RG_GRAV(a) a[IU] += g.hgx; a[IV] += g.hgy; a[IW] += g.hgz
-        RG_GRAV(qmx); RG_GRAV(qpx); RG_GRAV(qmy); RG_GRAV(qpy); RG_GRAV(qmz_new); RG_GRAV(qpz);
-#undef RG_GRAV
-      }
-#pragma unroll
-      for (int n = 0; n < NV; ++n) { L.qm[0][n][tj][ti] = qmx[n]; L.qm[1][n][tj][ti] = qmy[n]; }
+    for (int d = 0; d < 3; ++d) {
+      hydro_face_grid<+1, NV>(g, tq, h[d], grav, g.hgx, g.hgy, g.hgz, qm[d]);
+      hydro_face_grid<-1, NV>(g, tq, h[d], grav, g.hgx, g.hgy, g.hgz, qp[d]);
     }
+#pragma unroll
+    for (int n = 0; n < NV; ++n) { L.qm[0][n][tj][ti] = qm[0][n]; L.qm[1][n][tj][ti] = qm[1][n]; }
     __syncthreads();
 
-    // ---- C: Riemann problems at the three low faces of cell (i,j,kk)  (hydro_flux_cell) ----
+    // ---- C: Riemann problems at the three low faces of cell (i,j,kk); along z the left state is this column's own qm_z of the
+    // previous plane ----
     double fx[NV], fy[NV], fz[NV];
     {
       const int tim = ti > 0 ? ti - 1 : 0, tjm = tj > 0 ? tj - 1 : 0;
-      double ql[NV], qr[NV];
-      // x: normal frame = grid frame
+      double ql[NV];
 #pragma unroll
-      for (int n = 0; n < NV; ++n) { ql[n] = L.qm[0][n][tj][tim]; qr[n] = qpx[n]; fx[n] = 0.0; }
-      hydro_riemann<NV>(g, ql, qr, fx);
-      // y: IU <-> IV
-      ql[ID] = L.qm[1][ID][tjm][ti]; ql[IP] = L.qm[1][IP][tjm][ti]; ql[IU] = L.qm[1][IV][tjm][ti]; ql[IV] = L.qm[1][IU][tjm][ti]; ql[IW] = L.qm[1][IW][tjm][ti];
-      qr[ID] = qpy[ID]; qr[IP] = qpy[IP]; qr[IU] = qpy[IV]; qr[IV] = qpy[IU]; qr[IW] = qpy[IW];
+      for (int n = 0; n < NV; ++n) ql[n] = L.qm[0][n][tj][tim];
+      hydro_face_flux<0, NV>(g, ql, qp[0], fx);
 #pragma unroll
-      for (int n = 0; n < NV; ++n) fy[n] = 0.0;
-      hydro_riemann<NV>(g, ql, qr, fy);
-      // z: IU <-> IW; the left state is this column's own qm_z of the previous plane
-      ql[ID] = qmz[ID]; ql[IP] = qmz[IP]; ql[IU] = qmz[IW]; ql[IV] = qmz[IV]; ql[IW] = qmz[IU];
-      qr[ID] = qpz[ID]; qr[IP] = qpz[IP]; qr[IU] = qpz[IW]; qr[IV] = qpz[IV]; qr[IW] = qpz[IU];
+      for (int n = 0; n < NV; ++n) ql[n] = L.qm[1][n][tjm][ti];
+      hydro_face_flux<1, NV>(g, ql, qp[1], fy);
+      hydro_face_flux<2, NV>(g, qmz, qp[2], fz);
 #pragma unroll
-      for (int n = 0; n < NV; ++n) fz[n] = 0.0;
-      hydro_riemann<NV>(g, ql, qr, fz);
-#pragma unroll
-      for (int n = 0; n < NV; ++n) qmz[n] = qmz_new[n];
+      for (int n = 0; n < NV; ++n) qmz[n] = qm[2][n];
     }
 
     // ---- D: cell (i,j,kk-1) is complete once the flux through its high z face is known ----
     if (own && kk - 1 >= sa) {
       if (inner2d) {
-        up[ID] -= fz[ID] * dtdz; up[IP] -= fz[IP] * dtdz; up[IU] -= fz[IW] * dtdz; up[IV] -= fz[IV] * dtdz; up[IW] -= fz[IU] * dtdz;
-        if (g.grav_on) {   // momentum source with the mean of the old and new density (hydro_update_cell); energy untouched
-          const double rho_sum = rho_old + up[ID];
-          up[IU] += g.hgx * rho_sum; up[IV] += g.hgy * rho_sum; up[IW] += g.hgz * rho_sum;
-        }
-        if (dslot) {
-          double qn[NV];
-          const double cs = hydro_prim<NV>(g, up, qn);
-          inv_dt = fmax(inv_dt, (cs + fabs(qn[IU])) / g.dx + (cs + fabs(qn[IV])) / g.dy + (cs + fabs(qn[IW])) / g.dz);
-        }
+        hydro_apply_flux<2, -1, NV>(up, fz, dtdz);
+        if (grav) hydro_gravity_source<NV>(up, rho_old, g.hgx, g.hgy, g.hgz);
+        if (dslot) inv_dt = fmax(inv_dt, hydro_cfl_term<NV>(g, up));
       }
       double* o = Uout + idx2 + (size_t)(kk - 1) * sk;
 #pragma unroll
       for (int v = 0; v < NV; ++v) RG_STREAM_STORE(&o[v * N], up[v]);
     }
 
-    // ---- E: gather the x / y fluxes of plane kk  (hydro_update_cell; the high z flux follows in D of the next iteration) ----
+    // ---- E: gather the x / y fluxes of plane kk (the high z flux follows in D of the next iteration) ----
 #pragma unroll
     for (int n = 0; n < NV; ++n) { L.f[0][n][tj][ti] = fx[n]; L.f[1][n][tj][ti] = fy[n]; }
     if (kk < sb) {   // the same barrier publishes the primitives of plane kk+1 (L.q was last read before the barrier above)
@@ -355,20 +320,17 @@ __global__ void __launch_bounds__(TX * TY, MINW) hydro3d_sweep_kernel(DevParams 
       rho_old = uB[ID];
       if (own && inner2d) {
         const int tip = ti + 1 < TX ? ti + 1 : ti, tjp = tj + 1 < TY ? tj + 1 : tj;
-#define RG_LOW_X up[ID] += fx[ID] * dtdx; up[IP] += fx[IP] * dtdx; up[IU] += fx[IU] * dtdx; up[IV] += fx[IV] * dtdx; up[IW] += fx[IW] * dtdx
-#define RG_LOW_Y up[ID] += fy[ID] * dtdy; up[IP] += fy[IP] * dtdy; up[IU] += fy[IV] * dtdy; up[IV] += fy[IU] * dtdy; up[IW] += fy[IW] * dtdy
-#define RG_LOW_Z up[ID] += fz[ID] * dtdz; up[IP] += fz[IP] * dtdz; up[IU] += fz[IW] * dtdz; up[IV] += fz[IV] * dtdz; up[IW] += fz[IU] * dtdz
-#define RG_HIGH_X up[ID] -= L.f[0][ID][tj][tip] * dtdx; up[IP] -= L.f[0][IP][tj][tip] * dtdx; up[IU] -= L.f[0][IU][tj][tip] * dtdx; \
-                  up[IV] -= L.f[0][IV][tj][tip] * dtdx; up[IW] -= L.f[0][IW][tj][tip] * dtdx
-#define RG_HIGH_Y up[ID] -= L.f[1][ID][tjp][ti] * dtdy; up[IP] -= L.f[1][IP][tjp][ti] * dtdy; up[IU] -= L.f[1][IV][tjp][ti] * dtdy; \
-                  up[IV] -= L.f[1][IU][tjp][ti] * dtdy; up[IW] -= L.f[1][IW][tjp][ti] * dtdy
-        if (!g.dirwise_update) { RG_LOW_X; RG_LOW_Y; RG_LOW_Z; RG_HIGH_X; RG_HIGH_Y; }   // unsplitVersion 1: low faces, then high faces
-        else { RG_LOW_X; RG_HIGH_X; RG_LOW_Y; RG_HIGH_Y; RG_LOW_Z; }                     // unsplitVersion 2: direction by direction
-#undef RG_LOW_X
-#undef RG_LOW_Y
-#undef RG_LOW_Z
-#undef RG_HIGH_X
-#undef RG_HIGH_Y
+        double fxh[NV], fyh[NV];   // fluxes through the high x / y faces: the neighbours' low faces
+#pragma unroll
+        for (int n = 0; n < NV; ++n) { fxh[n] = L.f[0][n][tj][tip]; fyh[n] = L.f[1][n][tjp][ti]; }
+        if (!g.dirwise_update) {   // unsplitVersion 1: low faces, then high faces
+          hydro_apply_flux<0, +1, NV>(up, fx, dtdx); hydro_apply_flux<1, +1, NV>(up, fy, dtdy); hydro_apply_flux<2, +1, NV>(up, fz, dtdz);
+          hydro_apply_flux<0, -1, NV>(up, fxh, dtdx); hydro_apply_flux<1, -1, NV>(up, fyh, dtdy);
+        } else {                   // unsplitVersion 2: direction by direction
+          hydro_apply_flux<0, +1, NV>(up, fx, dtdx); hydro_apply_flux<0, -1, NV>(up, fxh, dtdx);
+          hydro_apply_flux<1, +1, NV>(up, fy, dtdy); hydro_apply_flux<1, -1, NV>(up, fyh, dtdy);
+          hydro_apply_flux<2, +1, NV>(up, fz, dtdz);
+        }
       }
     }
 

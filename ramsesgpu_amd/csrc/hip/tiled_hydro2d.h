@@ -8,21 +8,16 @@
 //
 // One thread per cell of a TX x TY tile (tiles overlap by one cell per side: the inner (TX-2) x (TY-2) threads finish a cell):
 //   phase 0  U of the cell -> primitives -> LDS (the one-cell ring around the tile by the first 2 TX + 2 TY threads)
-//   phase 1  slopes + trace of the cell (hydro_trace_cell); the states at its HIGH x / y faces -> LDS, the LOW ones stay in registers
-//   phase 2  Riemann problems at its LOW x / y faces (hydro_flux_cell) -> fluxes to LDS
-//   phase 3  update (hydro_update_cell: both update orders), uniform-gravity source, CFL term of the new cell into the device slots
-// Three barriers, 43 KB of LDS.  Same expressions, same operand order, same bits as the flat kernels.
+//   phase 1  slopes + trace of the cell; the states at its HIGH x / y faces -> LDS, the LOW ones stay in registers
+//   phase 2  Riemann problems at its LOW x / y faces -> fluxes to LDS
+//   phase 3  update (both update orders), uniform-gravity source, CFL term of the new cell into the device slots
+// Three barriers, 43 KB of LDS.  The arithmetic of phases 1-3 is the cell functions of kernels_hydro.h (hydro_half_slope,
+// hydro_trace_advance, hydro_face_grid, hydro_face_flux, hydro_apply_flux, hydro_gravity_source, hydro_cfl_term) that the flat
+// kernels call too: the same bits.  Tile geometry and LDS layout: tiled_hydro.h (HydroTile, tile_ring_cell, tile_owns, tile_inner).
 #pragma once
 #include "step_clock.h"
 
 namespace rgpu_tiled {
-
-template <int TX, int TY>
-struct Hydro2dTile {
-  double q[4][TY + 2][TX + 2];   // primitives: tile + ring
-  double qm[2][4][TY][TX];       // state at the HIGH x / y face of each cell (grid frame, floors and gravity predictor applied)
-  double f[2][4][TY][TX];        // flux through the LOW x / y face of each cell (face-normal frame)
-};
 
 // The ghost cells an interior cell is the source of, along one direction (bc_face_cell: dirichlet = mirror image with the normal
 // momentum negated, neumann = copies of the first / last interior cell, periodic = the image one period away).  x = the cell's index,
@@ -67,7 +62,7 @@ __global__ void __launch_bounds__(TX * TY) hydro2d_step_kernel(DevParams g, int 
   constexpr int NV = 4;
   constexpr int RING = 2 * TX + 2 * TY;
   static_assert(RING <= TX * TY, "ring cells are handled by the first RING threads");
-  __shared__ Hydro2dTile<TX, TY> L;
+  __shared__ HydroTile<TX, TY, NV> L;
 
   const int t = (int)threadIdx.x;
   const int by = (int)blockIdx.x / nbx, bx = (int)blockIdx.x - by * nbx;
@@ -77,9 +72,8 @@ __global__ void __launch_bounds__(TX * TY) hydro2d_step_kernel(DevParams g, int 
   const size_t N = g.ncell;
   const unsigned idx2 = ina ? (unsigned)i + (unsigned)j * g.sj : 0u;
   const int gw = g.gw;
-  // cells this thread writes: the inner threads of the tile, plus array row / column 0 (never inner cells)
-  const bool own = ina && ((ti >= 1 && ti < TX - 1) || i == 0) && ((tj >= 1 && tj < TY - 1) || j == 0);
-  const bool inner = i >= gw && i < g.isize - gw && j >= gw && j < g.jsize - gw;
+  const bool own = tile_owns<TX, TY>(ina, ti, tj, i, j);
+  const bool inner = tile_inner(g, i, j);
 
   // ---- phase 0: primitives of the tile and of its ring (corners excluded: no stencil reads them) ----
   double u[NV], q[NV];
@@ -91,10 +85,7 @@ __global__ void __launch_bounds__(TX * TY) hydro2d_step_kernel(DevParams g, int 
   }
   {
     int rti, rtj;
-    if (t < TX) { rti = t; rtj = -1; }
-    else if (t < 2 * TX) { rti = t - TX; rtj = TY; }
-    else if (t < 2 * TX + TY) { rti = -1; rtj = t - 2 * TX; }
-    else { rti = TX; rtj = t - 2 * TX - TY; }
+    tile_ring_cell<TX, TY>(t, rti, rtj);
     const int ri = bx * (TX - 2) + rti, rj = by * (TY - 2) + rtj;
     const bool ring = t < RING && ri >= 0 && ri < g.isize && rj >= 0 && rj < g.jsize;
     double ur[NV];
@@ -116,98 +107,62 @@ __global__ void __launch_bounds__(TX * TY) hydro2d_step_kernel(DevParams g, int 
   }
   __syncthreads();
 
-  // ---- phase 1: slopes and trace of the cell (hydro_trace_cell, ND = 2) ----
-  double qpx[NV], qpy[NV];
+  // ---- phase 1: slopes and trace of the cell; its high x / y face states -> LDS ----
+  double qp[2][NV];   // states at the low x / y face
   {
     const double st = g.slope_type;
-    const double gamma = g.gamma0;
-    double h[2][NV];
+    double h[2][NV], tq[NV], qm[2][NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const double nb[2][2] = {{L.q[v][tj + 1][ti], L.q[v][tj + 1][ti + 2]}, {L.q[v][tj][ti + 1], L.q[v][tj + 2][ti + 1]}};
 #pragma unroll
-      for (int d = 0; d < 2; ++d) {
-        double s;
-        if (st == 0) s = 0.0;
-        else s = tvd_half_slope(st, nb[d][0], q[v], nb[d][1]);
-        h[d][v] = s;
-      }
+      for (int d = 0; d < 2; ++d) h[d][v] = hydro_half_slope<2>(st, nb[d][0], q[v], nb[d][1]);
     }
-    const double r = q[ID], p = q[IP], uu = q[IU], vv = q[IV];
-    const double drx = h[0][ID], dpx = h[0][IP], dux = h[0][IU], dvx = h[0][IV];
-    const double dry = h[1][ID], dpy = h[1][IP], duy = h[1][IU], dvy = h[1][IV];
-    const rg_recip_t inv_r = rg_recip(r);
-    const double sr0 = (-uu * drx - dux * r) * dtdx + (-vv * dry - dvy * r) * dtdy;
-    const double su0 = (-uu * dux - rg_div(dpx, inv_r)) * dtdx + (-vv * duy) * dtdy;
-    const double sv0 = (-uu * dvx) * dtdx + (-vv * dvy - rg_div(dpy, inv_r)) * dtdy;
-    const double sp0 = (-uu * dpx - dux * gamma * p) * dtdx + (-vv * dpy - dvy * gamma * p) * dtdy;
-    double tq[NV];
-    tq[ID] = r + sr0; tq[IU] = uu + su0; tq[IV] = vv + sv0; tq[IP] = p + sp0;
-    // face states with the floors of trace.h:388-389 (hydro_face_state), grid frame
-    double qmx[NV], qmy[NV];
+    hydro_trace_advance<2, NV>(g, q, h, dtdx, dtdy, 0.0, tq);
 #pragma unroll
-    for (int n = 0; n < NV; ++n) {
-      qmx[n] = tq[n] + h[0][n]; qpx[n] = tq[n] - h[0][n];
-      qmy[n] = tq[n] + h[1][n]; qpy[n] = tq[n] - h[1][n];
-    }
-#define RG_FLOOR(a) a[ID] = fmax(g.smallr, a[ID]); a[IP] = fmax(g.smallp * a[ID], a[IP])
-    RG_FLOOR(qmx); RG_FLOOR(qpx); RG_FLOOR(qmy); RG_FLOOR(qpy);
-#undef RG_FLOOR
-    if (g.grav_on) {   // uniform static gravity: predictor on the traced states, after the floors (hydro_face_state)
-#define RG_GRAV(a) a[IU] += g.hgx; a[IV] += g.hgy
-      RG_GRAV(qmx); RG_GRAV(qpx); RG_GRAV(qmy); RG_GRAV(qpy);
-#undef RG_GRAV
+    for (int d = 0; d < 2; ++d) {
+      hydro_face_grid<+1, NV>(g, tq, h[d], g.grav_on, g.hgx, g.hgy, 0.0, qm[d]);
+      hydro_face_grid<-1, NV>(g, tq, h[d], g.grav_on, g.hgx, g.hgy, 0.0, qp[d]);
     }
 #pragma unroll
-    for (int n = 0; n < NV; ++n) { L.qm[0][n][tj][ti] = qmx[n]; L.qm[1][n][tj][ti] = qmy[n]; }
+    for (int n = 0; n < NV; ++n) { L.qm[0][n][tj][ti] = qm[0][n]; L.qm[1][n][tj][ti] = qm[1][n]; }
   }
   __syncthreads();
 
-  // ---- phase 2: Riemann problems at the two low faces of the cell (hydro_flux_cell) ----
+  // ---- phase 2: Riemann problems at the two low faces of the cell ----
   double fx[NV], fy[NV];
   {
     const int tim = ti > 0 ? ti - 1 : 0, tjm = tj > 0 ? tj - 1 : 0;
-    double ql[NV], qr[NV];
-    // x: normal frame = grid frame
+    double ql[NV];
 #pragma unroll
-    for (int n = 0; n < NV; ++n) { ql[n] = L.qm[0][n][tj][tim]; qr[n] = qpx[n]; fx[n] = 0.0; }
-    hydro_riemann<NV>(g, ql, qr, fx);
-    // y: IU <-> IV
-    ql[ID] = L.qm[1][ID][tjm][ti]; ql[IP] = L.qm[1][IP][tjm][ti]; ql[IU] = L.qm[1][IV][tjm][ti]; ql[IV] = L.qm[1][IU][tjm][ti];
-    qr[ID] = qpy[ID]; qr[IP] = qpy[IP]; qr[IU] = qpy[IV]; qr[IV] = qpy[IU];
+    for (int n = 0; n < NV; ++n) ql[n] = L.qm[0][n][tj][tim];
+    hydro_face_flux<0, NV>(g, ql, qp[0], fx);
 #pragma unroll
-    for (int n = 0; n < NV; ++n) fy[n] = 0.0;
-    hydro_riemann<NV>(g, ql, qr, fy);
+    for (int n = 0; n < NV; ++n) ql[n] = L.qm[1][n][tjm][ti];
+    hydro_face_flux<1, NV>(g, ql, qp[1], fy);
 #pragma unroll
     for (int n = 0; n < NV; ++n) { L.f[0][n][tj][ti] = fx[n]; L.f[1][n][tj][ti] = fy[n]; }
   }
   __syncthreads();
 
-  // ---- phase 3: update (hydro_update_cell), CFL term of the new state ----
+  // ---- phase 3: update, CFL term of the new state ----
   double inv = 0.0;
   if (own) {
     const double rho_old = u[ID];
     if (inner) {
       const int tip = ti + 1 < TX ? ti + 1 : ti, tjp = tj + 1 < TY ? tj + 1 : tj;
-#define RG_LOW_X u[ID] += fx[ID] * dtdx; u[IP] += fx[IP] * dtdx; u[IU] += fx[IU] * dtdx; u[IV] += fx[IV] * dtdx
-#define RG_LOW_Y u[ID] += fy[ID] * dtdy; u[IP] += fy[IP] * dtdy; u[IU] += fy[IV] * dtdy; u[IV] += fy[IU] * dtdy
-#define RG_HIGH_X u[ID] -= L.f[0][ID][tj][tip] * dtdx; u[IP] -= L.f[0][IP][tj][tip] * dtdx; u[IU] -= L.f[0][IU][tj][tip] * dtdx; u[IV] -= L.f[0][IV][tj][tip] * dtdx
-#define RG_HIGH_Y u[ID] -= L.f[1][ID][tjp][ti] * dtdy; u[IP] -= L.f[1][IP][tjp][ti] * dtdy; u[IU] -= L.f[1][IV][tjp][ti] * dtdy; u[IV] -= L.f[1][IU][tjp][ti] * dtdy
-      if (!g.dirwise_update) { RG_LOW_X; RG_LOW_Y; RG_HIGH_X; RG_HIGH_Y; }   // unsplitVersion 1: low faces, then high faces
-      else { RG_LOW_X; RG_HIGH_X; RG_LOW_Y; RG_HIGH_Y; }                     // unsplitVersion 2: direction by direction
-#undef RG_LOW_X
-#undef RG_LOW_Y
-#undef RG_HIGH_X
-#undef RG_HIGH_Y
-      if (g.grav_on) {   // momentum source with the mean of the old and new density; energy untouched
-        const double rho_sum = rho_old + u[ID];
-        u[IU] += g.hgx * rho_sum; u[IV] += g.hgy * rho_sum;
+      double fxh[NV], fyh[NV];   // fluxes through the high x / y faces: the neighbours' low faces
+#pragma unroll
+      for (int n = 0; n < NV; ++n) { fxh[n] = L.f[0][n][tj][tip]; fyh[n] = L.f[1][n][tjp][ti]; }
+      if (!g.dirwise_update) {   // unsplitVersion 1: low faces, then high faces
+        hydro_apply_flux<0, +1, NV>(u, fx, dtdx); hydro_apply_flux<1, +1, NV>(u, fy, dtdy);
+        hydro_apply_flux<0, -1, NV>(u, fxh, dtdx); hydro_apply_flux<1, -1, NV>(u, fyh, dtdy);
+      } else {                   // unsplitVersion 2: direction by direction
+        hydro_apply_flux<0, +1, NV>(u, fx, dtdx); hydro_apply_flux<0, -1, NV>(u, fxh, dtdx);
+        hydro_apply_flux<1, +1, NV>(u, fy, dtdy); hydro_apply_flux<1, -1, NV>(u, fyh, dtdy);
       }
-      if (dt_slots) {
-        double qn[NV];
-        const double cs = hydro_prim<NV>(g, u, qn);
-        inv = (cs + fabs(qn[IU])) / g.dx + (cs + fabs(qn[IV])) / g.dy;
-      }
+      if (g.grav_on) hydro_gravity_source<NV>(u, rho_old, g.hgx, g.hgy, 0.0);
+      if (dt_slots) inv = hydro_cfl_term<NV>(g, u);
     }
     if (!images) {
 #pragma unroll

@@ -294,26 +294,7 @@ RG_DEVFN void fill_xy_cell(const DevParams& g, const FillXY f, double* __restric
   }
 }
 
-// ---- CFL scan: value of one cell, 0 outside the interior (all contributions are >= 0) ----------------------
-template <int NV>
-RG_DEVFN double hydro_invdt_cell(const DevParams& g, const double* __restrict__ U, unsigned idx) {
-  const IJK c = unflatten(g, idx);
-  const int gw = g.gw;
-  if (c.i < gw || c.i >= g.isize - gw || c.j < gw || c.j >= g.jsize - gw) return 0.0;
-  if (NV == 5 && (c.k < gw || c.k >= g.ksize - gw)) return 0.0;
-  const size_t N = g.ncell;
-  double u[NV], q[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) u[v] = U[idx + v * N];
-  const double cs = hydro_prim<NV>(g, u, q);
-  const double vx = cs + fabs(q[IU]), vy = cs + fabs(q[IV]);
-  if (NV == 5) {
-    const double vz = cs + fabs(q[IW]);
-    return vx / g.dx + vy / g.dy + vz / g.dz;
-  }
-  return vx / g.dx + vy / g.dy;
-}
-
+// ---- CFL scan: value of one cell, 0 outside the interior (all contributions are >= 0); hydro: kernels_hydro.h ----
 RG_DEVFN double mhd_invdt_cell(const DevParams& g, const double* __restrict__ U, unsigned idx) {
   const IJK c = unflatten(g, idx);
   const int gw = g.gw;
