@@ -377,6 +377,60 @@ int rgpu_clock_stopped(rgpu_ctx* c);
  * a rank that failed in an unbatched step has told the others through ONE poisoned all-reduce and left the loop. */
 int rgpu_clock_check(rgpu_ctx* c);
 
+/* ---- ensembles of 2D boxes ----------------------------------------------------------------------------------------------------
+ * A fused 2D step is one kernel of 20-50 us that fills a fraction of the device (a 128^2 hydro box: ~100 of ~768 resident workgroups)
+ * and 2D boxes do not shard (rgpu_comm.h).  What fills the device is MANY boxes: seeds of a perturbation, a parameter scan.  An
+ * ensemble is `members` boxes of one shape and one solver configuration (*p, shared), each with its own state, its own dt sequence
+ * and its own end time, advanced by ONE step-kernel launch and ONE clock-kernel launch per step for all of them
+ * (csrc/hip/ensemble2d.h: the member is the second grid dimension; the kernels run the single-box body, hence the same doubles).
+ *
+ *   rgpu_ensemble_create   2D only (nz_global == 1) with slab_count == 1, else RGPU_EUNSUPPORTED; members outside
+ *                          1 .. RGPU_ENSEMBLE_MAX_MEMBERS: RGPU_EINVAL; no device: RGPU_ENODEVICE, as rgpu_create.  *out is returned
+ *                          even on failure so that rgpu_ensemble_last_error can be read; the caller destroys it.
+ *   rgpu_ensemble_member   member m as an ordinary rgpu_ctx over a slice of the ensemble's storage, on the ensemble's one stream
+ *                          (BORROWED; NULL when m is out of range).  Every entry point of this header works on it unchanged --
+ *                          rgpu_upload, rgpu_download, rgpu_make_all_boundaries, rgpu_compute_dt, rgpu_state_checksum, rgpu_read_cell,
+ *                          rgpu_set_gravity_field, the histories, and rgpu_one_step_integration / rgpu_run_steps on that member alone --
+ *                          except rgpu_destroy, which refuses a member (it returns without doing anything).
+ *   rgpu_ensemble_destroy  frees the members and everything else.
+ *   rgpu_ensemble_device_bytes   device memory of an ensemble (0: parameters rgpu_ensemble_create would refuse): what create allocates
+ *                          plus the clock records of the fused rounds (RGPU_CLOCK_BATCH records of 128 bytes per member, allocated by
+ *                          the first rgpu_ensemble_run_steps that takes a fused round, and as many again in pinned host memory).
+ *   rgpu_ensemble_run_steps      for EVERY member m exactly what rgpu_run_steps_log(member m, nsteps, tEnd[m], &nStep[m], &t[m], &dt[m],
+ *                          dt_log + m * nsteps) does on a lone context holding that member's state: the same states, nStep, t, dt and
+ *                          dt sequence -- bit for bit in librgpu.so, to round-off (relative L2 <= 1e-12; mostly, not always, the same bits)
+ *                          in librgpu_fast.so.  nStep, t, dt: [members], in / out.  tEnd: [members], or
+ *                          NULL for "no end".  dt_log: [members][nsteps] or NULL.  done[m] = steps member m took in this call.
+ *                          stop[m] (may be NULL) = 0, or why member m took fewer than nsteps: 1 = its t reached its tEnd (also when that
+ *                          happened with its last step, or before the call: done[m] = 0), 2 = its dt is not a number, 3 = its 1/dt is
+ *                          not finite (the codes of rgpu_clock_close).  A member stops with the last state it wrote while the others go
+ *                          on.  Codes 2 and 3 are that member's business: the call still returns RGPU_OK, the code is in stop[m] and
+ *                          the text in rgpu_last_error(member).  *fused_steps (may be NULL) = the step rounds that went through the
+ *                          fused launch.  Returns RGPU_OK or a negative code (a launch or a plain single-member step failed: the
+ *                          members are advanced for the steps that did run, as rgpu_run_steps_log does).
+ * The fused launch covers what rgpu_device_time_step_ready covers on a 2D context (2D hydro with Dirichlet, Neumann or periodic faces,
+ * no jet, no gravity; 2D MHD in an all-periodic non-rotating box; options step_clock, ghost_images and the tiled kernels on) and is
+ * used for a round when every member that still runs is ready and the running members share a step parity; every other round -- each
+ * member's first step of a run, uncovered configurations, members of mixed parity after different end times -- is taken member by
+ * member through the single-context loop: a correct fallback, not an error.  One more state is mixed in that sense and nothing
+ * re-aligns it: a 2D hydro member that was clock-ready when it was stepped ALONE (rgpu_run_steps on that member, or a member-by-member
+ * round beside a member whose state had just been uploaded) has rotated through its three CFL slot arrays, because the lone loop folds
+ * the clock into the step kernel on small grids; the fused launch addresses one array for all members, so from then on members whose
+ * arrays differ are stepped one by one -- for the rest of that call and of later ones, until every member is uploaded afresh.
+ * *fused_steps < the rounds taken (less each member's first) is how a caller sees it.  Batches of at most RGPU_CLOCK_BATCH rounds, one
+ * read-back of the records per batch.  Afterwards every member's bookkeeping (CFL slots, ghost cells) is what the single-context
+ * loop would have left: any later call on a member alone continues correctly. */
+typedef struct rgpu_ensemble rgpu_ensemble;
+#define RGPU_ENSEMBLE_MAX_MEMBERS 1024
+int rgpu_ensemble_create(const rgpu_params* p, int members, rgpu_ensemble** out);
+void rgpu_ensemble_destroy(rgpu_ensemble* e);
+int rgpu_ensemble_members(rgpu_ensemble* e);
+rgpu_ctx* rgpu_ensemble_member(rgpu_ensemble* e, int m);
+size_t rgpu_ensemble_device_bytes(const rgpu_params* p, int members);
+const char* rgpu_ensemble_last_error(rgpu_ensemble* e);
+int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, int* nStep, double* t, double* dt, double* dt_log, int* done,
+                            int* stop, int* fused_steps);
+
 /* Self-test of the device arithmetic the parity contract rests on: for n operand pairs computes on the device
  *   quot[i]  = rg_div(num[i], rg_recip(den[i]))   the shared-reciprocal division of csrc/hip/rg_backend.h
  *   quot2[i] = num[i] / den[i]                    the compiler's IEEE division

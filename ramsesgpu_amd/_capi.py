@@ -204,6 +204,28 @@ def declare_device_api(lib):
     return lib
 
 
+def declare_ensemble_api(lib):
+    """prototypes of the rgpu_ensemble_* entry points (include/rgpu.h, "ensembles of 2D boxes")"""
+    P = C.POINTER(RgpuParams)
+    ens = C.c_void_p
+    int_p = C.POINTER(C.c_int)
+    lib.rgpu_ensemble_create.restype = C.c_int
+    lib.rgpu_ensemble_create.argtypes = [P, C.c_int, C.POINTER(ens)]
+    lib.rgpu_ensemble_destroy.restype = None
+    lib.rgpu_ensemble_destroy.argtypes = [ens]
+    lib.rgpu_ensemble_members.restype = C.c_int
+    lib.rgpu_ensemble_members.argtypes = [ens]
+    lib.rgpu_ensemble_member.restype = C.c_void_p
+    lib.rgpu_ensemble_member.argtypes = [ens, C.c_int]
+    lib.rgpu_ensemble_device_bytes.restype = C.c_size_t
+    lib.rgpu_ensemble_device_bytes.argtypes = [P, C.c_int]
+    lib.rgpu_ensemble_last_error.restype = C.c_char_p
+    lib.rgpu_ensemble_last_error.argtypes = [ens]
+    lib.rgpu_ensemble_run_steps.restype = C.c_int
+    lib.rgpu_ensemble_run_steps.argtypes = [ens, C.c_int, c_double_p, int_p, c_double_p, c_double_p, c_double_p, int_p, int_p, int_p]
+    return lib
+
+
 # every symbol include/rgpu.h declares (checked by tests/test_abi.py against the built library)
 DECLARED_SYMBOLS = [
     "rgpu_create", "rgpu_create_external", "rgpu_destroy", "rgpu_state_elems", "rgpu_device_bytes", "rgpu_last_error",
@@ -213,4 +235,5 @@ DECLARED_SYMBOLS = [
     "rgpu_step_post_a", "rgpu_step_post_b", "rgpu_one_step_integration", "rgpu_run_steps", "rgpu_run_steps_log", "rgpu_device_time_step_ready", "rgpu_clock_capable", "rgpu_clock_open", "rgpu_clock_tick", "rgpu_clock_close", "rgpu_clock_stopped", "rgpu_clock_check", "rgpu_set_option", "rgpu_get_option", "rgpu_synchronize",
     "rgpu_enable_timers", "rgpu_get_timers", "rgpu_reset_timers", "rgpu_timer_name", "rgpu_dominant_kernel",
     "rgpu_backend_name", "rgpu_arithmetic", "rgpu_selftest_arith", "rgpu_selftest_alfven", "rgpu_step_ou_forcing", "rgpu_ou_forcing_state", "rgpu_ou_forcing_get_state", "rgpu_ou_forcing_set_state", "rgpuh_params_from_ini", "rgpuh_run_settings", "rgpuh_init_condition", "rgpuh_init_gravity", "rgpu_set_gravity_field", "rgpuh_init_forcing", "rgpu_set_forcing_field", "rgpu_forcing_sums", "rgpu_add_forcing", "rgpuh_run", "rgpuh_run_hooked",
+    "rgpu_ensemble_create", "rgpu_ensemble_destroy", "rgpu_ensemble_members", "rgpu_ensemble_member", "rgpu_ensemble_device_bytes", "rgpu_ensemble_last_error", "rgpu_ensemble_run_steps",
 ]

@@ -69,6 +69,7 @@ struct rgpu_ctx {
   unsigned long long* d_red_base;   // 3 x RG_DT_SLOTS
   bool fold_mode, fold_pending; int fold_phase0; ClockFold fold;
   bool fold_request;            // set by rgpu_run_steps_log around its own rgpu_clock_open (clock_ready holds there): a batch opened from outside never folds
+  bool borrowed;                // member of an rgpu_ensemble (api/entry_ensemble.h): state and slot arrays are slices of the ensemble's, rgpu_destroy refuses
   std::string err;
 };
 
@@ -229,7 +230,8 @@ int alloc_zero(rgpu_ctx* c, double** ptr, size_t doubles) {
   return rg_memset_async(*ptr, 0, doubles * sizeof(double), c->stream);
 }
 
-int create_common(const rgpu_params* p, double* dU, double* dU2, void* hip_stream, bool external, rgpu_ctx** out) {
+// slots != 0 (members of an ensemble): 3 x RG_DT_SLOTS device slots the context uses instead of allocating its own
+int create_common(const rgpu_params* p, double* dU, double* dU2, void* hip_stream, bool external, rgpu_ctx** out, unsigned long long* slots = 0) {
   if (!out) return RGPU_EINVAL;
   *out = 0;
   std::string why;
@@ -240,6 +242,7 @@ int create_common(const rgpu_params* p, double* dU, double* dU2, void* hip_strea
   std::memset(&c->p, 0, sizeof(c->p));
   if (p) c->p = *p;
   c->own_state = !external;
+  c->borrowed = false;
   c->U[0] = c->U[1] = 0;
   c->Q = c->E = c->T = c->F = c->emf = c->shear_save = c->shear_remap = 0;
   c->G = 0;
@@ -295,7 +298,8 @@ int create_common(const rgpu_params* p, double* dU, double* dU2, void* hip_strea
       return fail(c, RGPU_ENOMEM, "device allocation of the shear buffers failed");
   }
   static_assert((int)RG_DT_SLOTS == RGPU_DT_SLOTS, "include/rgpu.h promises RGPU_DT_SLOTS device slots");
-  if (rg_malloc((void**)&c->d_red_base, 3 * RG_DT_SLOTS * sizeof(unsigned long long)) || rg_host_alloc((void**)&c->h_red, RG_DT_SLOTS * sizeof(unsigned long long)) ||
+  if (slots) { c->d_red_base = slots; c->borrowed = true; }
+  if ((!slots && rg_malloc((void**)&c->d_red_base, 3 * RG_DT_SLOTS * sizeof(unsigned long long))) || rg_host_alloc((void**)&c->h_red, RG_DT_SLOTS * sizeof(unsigned long long)) ||
       rg_memset_async(c->d_red_base, 0, 3 * RG_DT_SLOTS * sizeof(unsigned long long), c->stream))
     return fail(c, RGPU_ENOMEM, "allocation of the reduction slots failed");
   c->d_red = c->d_red_base;

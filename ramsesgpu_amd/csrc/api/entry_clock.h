@@ -136,9 +136,10 @@ int rgpu_clock_close(rgpu_ctx* c, int nStep0, int* ran, double* t, double* dt_la
   return RGPU_OK;
 }
 
-int rgpu_run_steps_log(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log) {
-  RG_CHECK_CTX(c);
-  if (!nStep || !t || !dt) return fail(c, RGPU_EINVAL, "run_steps: null pointer");
+// rgpu_run_steps_log; *why = 0, or the stop code of the record that ended the run (1: tEnd, 2: dt is not a number, 3: 1/dt is not
+// finite -- the last two are also reported as RGPU_EHIP)
+static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int* why) {
+  *why = 0;
   int done = 0;
   while (done < nsteps && *t < tEnd) {
     const int parity = *nStep % 2;
@@ -176,11 +177,19 @@ int rgpu_run_steps_log(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double*
     done += ran;
     if (rc) { c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps: queueing a device-clock step: " + launch_err); }
     if (ran < queued) {
+      *why = stop;
       if (stop >= 2) return fail(c, RGPU_EHIP, stop == 2 ? "run_steps: the time step is not a number" : "run_steps: 1/dt is not finite");
       break;
     }
   }
   return done;
+}
+
+int rgpu_run_steps_log(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log) {
+  RG_CHECK_CTX(c);
+  if (!nStep || !t || !dt) return fail(c, RGPU_EINVAL, "run_steps: null pointer");
+  int why = 0;
+  return run_steps_impl(c, nsteps, tEnd, nStep, t, dt, dt_log, &why);
 }
 
 int rgpu_run_steps(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt) {

@@ -9,7 +9,7 @@ int rgpu_create_external(const rgpu_params* p, double* dU, double* dU2, void* hi
 }
 
 void rgpu_destroy(rgpu_ctx* c) {
-  if (!c) return;
+  if (!c || c->borrowed) return;   // (a member of an ensemble belongs to it: rgpu_ensemble_destroy)
   if (c->device >= 0) rg_set_device(c->device);
   if (c->own_state) { rg_free(c->U[0]); rg_free(c->U[1]); }
   rg_free(c->Q); rg_free(c->E); rg_free(c->T); rg_free(c->F); rg_free(c->emf); rg_free(c->shear_save); rg_free(c->shear_remap); rg_free(c->G); rg_free(c->Frc);

@@ -287,7 +287,7 @@ int rgpu_comm_create(rgpu_ctx* ctx, int rank, int nranks, const char id[RGPU_COM
   cm->fuse_scan = false; cm->clock_ok = false; cm->poisoned = 0; cm->exchanges_posted = 0; cm->exchanges_expected = 0; cm->clocked_steps = 0;
   if (!ctx || !id || nranks < 1 || rank < 0 || rank >= nranks) return fail(cm, RGPU_EINVAL, "comm_create: bad arguments");
   if (rgpu_get_params(ctx, &cm->p)) return fail(cm, RGPU_EINVAL, "comm_create: no parameters in the context");
-  if (cm->p.nz_global == 1) return fail(cm, RGPU_EUNSUPPORTED, "2D problems do not shard: run replicas");
+  if (cm->p.nz_global == 1) return fail(cm, RGPU_EUNSUPPORTED, "2D problems do not shard: many 2D boxes on one device are an ensemble (rgpu_ensemble_create, rgpu.h)");
   if (cm->p.slab_rank != rank || cm->p.slab_count != nranks) return fail(cm, RGPU_EINVAL, "comm_create: the context was created for another slab_rank / slab_count");
   (void)rgpu_stream_handle(ctx);   // makes the context's device current (every rgpu entry point does)
   if (rgpu_transport::create(&cm->tc, rank, nranks, id)) return fail(cm, RGPU_EHIP, "transport: " + (cm->tc ? cm->tc->err : std::string("allocation")));

@@ -3,9 +3,13 @@
 //   rgpu_tiled::mhd3d_sweep(...)        trace + Riemann problems of the 3D MHD step for a plane range
 //   rgpu_tiled::mhd2d_step(...)         whole 2D MHD step
 //   rgpu_tiled::hydro2d_step(...)       whole 2D hydro step
+//   rgpu_tiled::hydro2d_ensemble_step(...) / mhd2d_ensemble_step(...)   the same for every member of an ensemble of 2D boxes (ensemble2d.h)
 // each returning 0 = done, 1 = configuration not covered (the driver runs the flat per-cell kernels), < 0 = error.
 #pragma once
 #include "tiled_hydro.h"
 #include "tiled_mhd.h"
 #include "tiled_mhd2d.h"
 #include "tiled_hydro2d.h"
+#include "ensemble2d.h"
+// the ensemble kernels exist (api/entry_ensemble.h: without this macro -- the test-only host emulation -- an ensemble steps member by member)
+#define RGPU_TILED_ENSEMBLE2D 1

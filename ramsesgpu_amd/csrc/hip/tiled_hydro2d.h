@@ -46,19 +46,12 @@ RG_DEVFN ImgDim images_of(int x, int n, int gw, int bc_lo, int bc_hi) {
 // periodic, no jet, nothing modifies the new state after this kernel): the interior cells also write the ghost cells the next
 // step's ghost fill (X, then Y over the full extent: corners are images of images) would copy them into -- the same doubles -- and
 // the ghost cells' own threads do not store: one writer per location, and that fill is not launched (StateRecord::ghosts_written).
+// The body is a device function of its own: the single-box kernel below and the ensemble kernel (ensemble2d.h: many boxes of one
+// shape in one launch, the member in blockIdx.y) call it -- one copy of the numerics, the tile of a workgroup from blockIdx.x alone,
+// the time step by value (where it comes from -- arguments, a device record, the folded clock -- is the calling kernel's business).
 template <int TX, int TY, int SPEC>
-__global__ void __launch_bounds__(TX * TY) hydro2d_step_kernel(DevParams g, int nbx, const double* __restrict__ Uin, double* __restrict__ Uout,
-                                                               double dtdx, double dtdy, unsigned long long* dt_slots, int images, const StepClock* clk, ClockFold fold) {
-  spec_assume<SPEC>(g);
-  if (fold.out) {   // the clock of this step is part of the kernel (step_clock.h: clock_fold)
-    __shared__ double Lred[TX * TY / 64];
-    const StepClock r = clock_fold<TX * TY>(fold, Lred);
-    if (r.stop) return;
-    dtdx = rg_uniform(r.dtdx); dtdy = rg_uniform(r.dtdy);
-  } else if (clk) {   // the time step lives on the device (hip/step_clock.h)
-    if (clk->stop) return;
-    dtdx = clk->dtdx; dtdy = clk->dtdy;
-  }
+__device__ __forceinline__ void hydro2d_step_body(const DevParams& g, int nbx, const double* __restrict__ Uin, double* __restrict__ Uout,
+                                                  double dtdx, double dtdy, unsigned long long* dt_slots, int images) {
   constexpr int NV = 4;
   constexpr int RING = 2 * TX + 2 * TY;
   static_assert(RING <= TX * TY, "ring cells are handled by the first RING threads");
@@ -184,6 +177,22 @@ __global__ void __launch_bounds__(TX * TY) hydro2d_step_kernel(DevParams g, int 
     }
   }
   if (dt_slots) rgpu::rg_slot_max_wave(dt_slots + (((unsigned)blockIdx.x * (unsigned)(TX * TY / 64) + (unsigned)(t >> 6)) & (rgpu::RG_DT_SLOTS - 1)), inv);
+}
+
+template <int TX, int TY, int SPEC>
+__global__ void __launch_bounds__(TX * TY) hydro2d_step_kernel(DevParams g, int nbx, const double* __restrict__ Uin, double* __restrict__ Uout,
+                                                               double dtdx, double dtdy, unsigned long long* dt_slots, int images, const StepClock* clk, ClockFold fold) {
+  spec_assume<SPEC>(g);
+  if (fold.out) {   // the clock of this step is part of the kernel (step_clock.h: clock_fold)
+    __shared__ double Lred[TX * TY / 64];
+    const StepClock r = clock_fold<TX * TY>(fold, Lred);
+    if (r.stop) return;
+    dtdx = rg_uniform(r.dtdx); dtdy = rg_uniform(r.dtdy);
+  } else if (clk) {   // the time step lives on the device (hip/step_clock.h)
+    if (clk->stop) return;
+    dtdx = clk->dtdx; dtdy = clk->dtdy;
+  }
+  hydro2d_step_body<TX, TY, SPEC>(g, nbx, Uin, Uout, dtdx, dtdy, dt_slots, images);
 }
 
 template <int TX, int TY, int SPEC>

@@ -60,15 +60,13 @@ struct F2LdsRead {
   RG_DEVFN unsigned sj() const { return (unsigned)M2_FX; }
 };
 
+// The body is a device function of its own: the single-box kernel below and the ensemble kernel (ensemble2d.h: many boxes of one
+// shape in one launch, the member in blockIdx.y) call it -- one copy of the numerics, the tile of a workgroup from blockIdx.x alone,
+// the time step by value (where it comes from -- arguments, a device record, the folded clock -- is the calling kernel's business).
 template <int SPEC>
-__global__ void __launch_bounds__(M2_THREADS, 2) mhd2d_step_kernel(DevParams g, RotCoef rc, int nbx, const double* __restrict__ U,
-                                                                   double* __restrict__ Unew, double dt, double dtdx, double dtdy,
-                                                                   unsigned long long* dt_slots, int images, const StepClock* clk) {
-  spec_assume<SPEC>(g);
-  if (clk) {   // the time step lives on the device (hip/step_clock.h): a batch of steps queued without a host round trip
-    if (clk->stop) return;
-    dt = clk->dt; dtdx = clk->dtdx; dtdy = clk->dtdy;
-  }
+__device__ __forceinline__ void mhd2d_step_body(const DevParams& g, const RotCoef& rc, int nbx, const double* __restrict__ U,
+                                                double* __restrict__ Unew, double dt, double dtdx, double dtdy,
+                                                unsigned long long* dt_slots, int images) {
   __shared__ double LQ[8 * M2_ICELLS];          // primitives of the input tile; from phase 2 on: the fluxes F (13 x 128)
   __shared__ double LA[M2_ICELLS], LB[M2_ICELLS];   // face field Bx, By of the input tile
   __shared__ double LT[T2_COUNT * M2_TCELLS];   // compact traced state
@@ -190,6 +188,18 @@ __global__ void __launch_bounds__(M2_THREADS, 2) mhd2d_step_kernel(DevParams g, 
     }
     if (dt_slots) rgpu::rg_slot_max_wave(dt_slots + (((unsigned)blockIdx.x * 2u + (unsigned)(t >> 6)) & (rgpu::RG_DT_SLOTS - 1)), inv);
   }
+}
+
+template <int SPEC>
+__global__ void __launch_bounds__(M2_THREADS, 2) mhd2d_step_kernel(DevParams g, RotCoef rc, int nbx, const double* __restrict__ U,
+                                                                   double* __restrict__ Unew, double dt, double dtdx, double dtdy,
+                                                                   unsigned long long* dt_slots, int images, const StepClock* clk) {
+  spec_assume<SPEC>(g);
+  if (clk) {   // the time step lives on the device (hip/step_clock.h): a batch of steps queued without a host round trip
+    if (clk->stop) return;
+    dt = clk->dt; dtdx = clk->dtdx; dtdy = clk->dtdy;
+  }
+  mhd2d_step_body<SPEC>(g, rc, nbx, U, Unew, dt, dtdx, dtdy, dt_slots, images);
 }
 
 // Configurations the fused 2D step covers: no per-cell gravity field (its own instantiations) and no Dirichlet face (its ghost

@@ -27,4 +27,5 @@ using namespace rgpu_dev;
 #include "api/history.h"
 #include "api/entry_core.h"
 #include "api/entry_clock.h"
+#include "api/entry_ensemble.h"
 #include "api/entry_misc.h"

@@ -1,0 +1,93 @@
+"""An ensemble of 2D boxes on one GPU (rgpu_ensemble_*, include/rgpu.h): members of one shape and one solver configuration, each with
+its own state, dt sequence and end time, advanced by one step-kernel launch and one clock-kernel launch per step for all of them.
+No numerics live here: `Ensemble` owns the C object, `member(m)` is a `Solver` view of one member's borrowed context."""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from .solver import RgpuError, Solver, load_library
+
+
+class _Member(Solver):
+    """a Solver over a context the ensemble owns: every method of Solver works, close() leaves the context alone"""
+
+    def __init__(self, params, library, ctx):
+        self.L = library
+        self.lib = library.lib
+        self.p = params
+        self.ctx = C.c_void_p(ctx)
+        self.nStep = 0
+        self.totalTime = 0.0
+        self.dt = 0.0
+        self.dt_log = []
+
+    def close(self):
+        self.ctx = C.c_void_p()
+
+
+class Ensemble:
+    def __init__(self, params, members, library=None):
+        self.L = library or load_library()
+        self.lib = _capi.declare_ensemble_api(self.L.lib)
+        self.p = params
+        self.ens = C.c_void_p()
+        rc = self.lib.rgpu_ensemble_create(C.byref(params), int(members), C.byref(self.ens))
+        if rc:
+            msg = self.lib.rgpu_ensemble_last_error(self.ens).decode() if self.ens else "?"
+            self.close()
+            raise RgpuError("rgpu_ensemble_create failed (%d): %s" % (rc, msg))
+        self.members = self.lib.rgpu_ensemble_members(self.ens)
+        self._views = [_Member(params, self.L, self.lib.rgpu_ensemble_member(self.ens, m)) for m in range(self.members)]
+
+    def close(self):
+        for v in getattr(self, "_views", []):
+            v.close()
+        self._views = []
+        if getattr(self, "ens", None):
+            self.lib.rgpu_ensemble_destroy(self.ens)
+            self.ens = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def member(self, m):
+        """member m as a Solver (upload, getDataHost, compute_dt, state_checksum, oneStepIntegration, run_steps .. on that box alone);
+        its nStep / totalTime / dt / dt_log are the ones run_steps of the ensemble keeps"""
+        if not 0 <= m < self.members:
+            raise IndexError("member %d of %d" % (m, self.members))
+        return self._views[m]
+
+    def device_bytes(self):
+        return int(self.lib.rgpu_ensemble_device_bytes(C.byref(self.p), self.members))
+
+    def start(self, U0s):
+        """per member what Solver.start(U0, 0) does before its time loop: upload, ghost fill, the copy to the second array"""
+        assert len(U0s) == self.members, (len(U0s), self.members)
+        for v, U0 in zip(self._views, U0s):
+            v.start(U0, 0)
+
+    def run_steps(self, nsteps, tEnd=None):
+        """rgpu_ensemble_run_steps: up to nsteps steps of every member (tEnd: None, one end time for all, or one per member).
+        Returns (done, stop, fused_steps): per member the steps taken and 0 or why there were fewer (1: tEnd reached, 2 / 3: its time step
+        broke down), and the number of step rounds that went through the fused launch.  Every member view keeps its nStep, totalTime,
+        dt and the dt_log of this call."""
+        M, n = self.members, int(nsteps)
+        ns = (C.c_int * M)(*[v.nStep for v in self._views])
+        ts = (C.c_double * M)(*[v.totalTime for v in self._views])
+        ds = (C.c_double * M)(*[v.dt for v in self._views])
+        ends = None
+        if tEnd is not None:
+            ends = (C.c_double * M)(*([float(tEnd)] * M if np.isscalar(tEnd) else [float(x) for x in tEnd]))
+        log = (C.c_double * (M * max(n, 1)))()
+        done, stop, fused = (C.c_int * M)(), (C.c_int * M)(), C.c_int(0)
+        rc = self.lib.rgpu_ensemble_run_steps(self.ens, n, ends, ns, ts, ds, log, done, stop, C.byref(fused))
+        for m, v in enumerate(self._views):
+            v.nStep, v.totalTime, v.dt = ns[m], ts[m], ds[m]
+            v.dt_log = [log[m * n + i] for i in range(done[m])]
+        if rc:
+            raise RgpuError("rgpu_ensemble_run_steps failed (%d): %s" % (rc, self.lib.rgpu_ensemble_last_error(self.ens).decode()))
+        return list(done), list(stop), fused.value
