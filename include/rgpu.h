@@ -380,7 +380,8 @@ int rgpu_clock_check(rgpu_ctx* c);
 /* ---- ensembles of 2D boxes ----------------------------------------------------------------------------------------------------
  * A fused 2D step is one kernel of 20-50 us that fills a fraction of the device (a 128^2 hydro box: ~100 of ~768 resident workgroups)
  * and 2D boxes do not shard (rgpu_comm.h).  What fills the device is MANY boxes: seeds of a perturbation, a parameter scan.  An
- * ensemble is `members` boxes of one shape and one solver configuration (*p, shared), each with its own state, its own dt sequence
+ * ensemble is `members` boxes of one shape and one solver configuration (*p, shared -- or one set per member that differs in
+ * doubles only: rgpu_ensemble_create_scan, below), each with its own state, its own dt sequence
  * and its own end time, advanced by ONE step-kernel launch and ONE clock-kernel launch per step for all of them
  * (csrc/hip/ensemble2d.h: the member is the second grid dimension; the kernels run the single-box body, hence the same doubles).
  *
@@ -419,14 +420,35 @@ int rgpu_clock_check(rgpu_ctx* c);
  * arrays differ are stepped one by one -- for the rest of that call and of later ones, until every member is uploaded afresh.
  * *fused_steps < the rounds taken (less each member's first) is how a caller sees it.  Batches of at most RGPU_CLOCK_BATCH rounds, one
  * read-back of the records per batch.  Afterwards every member's bookkeeping (CFL slots, ghost cells) is what the single-context
- * loop would have left: any later call on a member alone continues correctly. */
+ * loop would have left: any later call on a member alone continues correctly.
+ *
+ * Parameter scans: rgpu_ensemble_create_scan takes one parameter set PER MEMBER (sets[m] for member m) instead of one for all.
+ *   Shared, because they select code or shape: every int32_t field of rgpu_params, slope_type, and the four sign classes cIso > 0,
+ *   Omega0 > 0, nu > 0, eta > 0.  A set that differs from sets[0] in one of them: RGPU_EINVAL, the message names the field and the
+ *   first offending member.  A set rgpu_ensemble_create would refuse: that call's code.  sets == NULL: RGPU_EINVAL.
+ *   May differ: every other double -- gamma0 (with smallp, smallpp, gamma6), cfl, cIso, smallr, smallc, smalle, the box extents and
+ *   dx, dy, the jet, gravity, viscosity and forcing magnitudes.
+ *   Everything else is the ensemble above: rgpu_ensemble_member / _members / _destroy / _last_error / _run_steps work unchanged, and
+ *   rgpu_ensemble_run_steps gives member m exactly what rgpu_run_steps_log gives a lone context created from sets[m] (bit for bit in
+ *   librgpu.so, relative L2 <= 1e-12 in librgpu_fast.so).  On the fused rounds every workgroup reads its member's constants
+ *   (DevParams, the clock's constants, the rotating-frame coefficients: 384 bytes per member) from a table in device memory through
+ *   scalar loads (csrc/hip/ensemble_scan.h) instead of the kernel arguments; the table is written once, by the first fused round, and
+ *   never again.  The same kernel bodies, the same placement on a CU as the uniform ensemble kernels in every instantiation (DESIGN
+ *   3.6.1: no retreat was needed for the generic 2D MHD kernel).  A scan whose sets are all bytewise equal takes the by-value
+ *   launch of rgpu_ensemble_create (unless option "member_params" is 1).  Where a configuration is off the fused path it is so for
+ *   all members alike, and the member-by-member rounds use each member's own context.
+ *   rgpu_ensemble_scan_device_bytes: 0 for input rgpu_ensemble_create_scan would refuse, else rgpu_ensemble_device_bytes of the
+ *   shared shape plus the table. */
 typedef struct rgpu_ensemble rgpu_ensemble;
 #define RGPU_ENSEMBLE_MAX_MEMBERS 1024
 int rgpu_ensemble_create(const rgpu_params* p, int members, rgpu_ensemble** out);
+/* members parameter sets, sets[m] for member m */
+int rgpu_ensemble_create_scan(const rgpu_params* sets, int members, rgpu_ensemble** out);
 void rgpu_ensemble_destroy(rgpu_ensemble* e);
 int rgpu_ensemble_members(rgpu_ensemble* e);
 rgpu_ctx* rgpu_ensemble_member(rgpu_ensemble* e, int m);
 size_t rgpu_ensemble_device_bytes(const rgpu_params* p, int members);
+size_t rgpu_ensemble_scan_device_bytes(const rgpu_params* sets, int members);
 const char* rgpu_ensemble_last_error(rgpu_ensemble* e);
 int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, int* nStep, double* t, double* dt, double* dt_log, int* done,
                             int* stop, int* fused_steps);
@@ -467,6 +489,8 @@ int rgpu_selftest_alfven(const rgpu_params* p, int n, const double* states36, do
  *   "xcd_sub" (-1)      sub-band size (cells) of the XCD-aware workgroup order of the flat kernels, read by rgpu_create; 0: linear
  *   "zseg" (0)          planes per z segment of the tiled sweeps; 0: planned per launch
  *   "chunks" (-1)       chunks of the two-stream schedule of the flat 3D MHD kernels, read by rgpu_create; 1: one stream
+ *   "member_params" (0) 1: the fused rounds of EVERY ensemble read their constants from the per-member table (the path of a
+ *                       parameter scan), even when all sets are equal: the table path and the by-value path on one workload
  * rgpu_set_option returns the previous value (-1: unknown name; the options above are never negative except "as created"). */
 int rgpu_set_option(const char* name, int value);
 int rgpu_get_option(const char* name);

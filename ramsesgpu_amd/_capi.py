@@ -211,6 +211,11 @@ def declare_ensemble_api(lib):
     int_p = C.POINTER(C.c_int)
     lib.rgpu_ensemble_create.restype = C.c_int
     lib.rgpu_ensemble_create.argtypes = [P, C.c_int, C.POINTER(ens)]
+    if hasattr(lib, "rgpu_ensemble_create_scan"):   # (absent from an older build of the library: scripts/ensemble_bench.py --baseline-lib)
+        lib.rgpu_ensemble_create_scan.restype = C.c_int        # P: an array of `members` parameter sets
+        lib.rgpu_ensemble_create_scan.argtypes = [P, C.c_int, C.POINTER(ens)]
+        lib.rgpu_ensemble_scan_device_bytes.restype = C.c_size_t
+        lib.rgpu_ensemble_scan_device_bytes.argtypes = [P, C.c_int]
     lib.rgpu_ensemble_destroy.restype = None
     lib.rgpu_ensemble_destroy.argtypes = [ens]
     lib.rgpu_ensemble_members.restype = C.c_int
@@ -236,4 +241,5 @@ DECLARED_SYMBOLS = [
     "rgpu_enable_timers", "rgpu_get_timers", "rgpu_reset_timers", "rgpu_timer_name", "rgpu_dominant_kernel",
     "rgpu_backend_name", "rgpu_arithmetic", "rgpu_selftest_arith", "rgpu_selftest_alfven", "rgpu_step_ou_forcing", "rgpu_ou_forcing_state", "rgpu_ou_forcing_get_state", "rgpu_ou_forcing_set_state", "rgpuh_params_from_ini", "rgpuh_run_settings", "rgpuh_init_condition", "rgpuh_init_gravity", "rgpu_set_gravity_field", "rgpuh_init_forcing", "rgpu_set_forcing_field", "rgpu_forcing_sums", "rgpu_add_forcing", "rgpuh_run", "rgpuh_run_hooked",
     "rgpu_ensemble_create", "rgpu_ensemble_destroy", "rgpu_ensemble_members", "rgpu_ensemble_member", "rgpu_ensemble_device_bytes", "rgpu_ensemble_last_error", "rgpu_ensemble_run_steps",
+    "rgpu_ensemble_create_scan", "rgpu_ensemble_scan_device_bytes",
 ]

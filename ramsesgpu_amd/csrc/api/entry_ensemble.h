@@ -3,6 +3,9 @@
 // time step on the device (entry_clock.h: clock_ready), by ONE step launch and ONE clock launch per step for all of them
 // (hip/ensemble2d.h); everywhere else member by member through the single-context loop.  Either way every member gets exactly what
 // rgpu_run_steps_log gives a lone context holding its state.
+// A parameter scan (rgpu_ensemble_create_scan) is the same object with one parameter set per member: the sets share what selects code
+// or shape (scan_validate), each member context is created from its own set, and the fused rounds read every member's constants from
+// a table on the device (hip/ensemble_scan.h) instead of handing one member's to the kernels by value.
 #pragma once
 
 struct rgpu_ensemble {
@@ -14,7 +17,12 @@ struct rgpu_ensemble {
 #ifdef RGPU_TILED_ENSEMBLE2D
   StepClock *d_clk, *h_clk;      // records of a batch, tick-major: tick n of member m at [n * members + m]
   rgpu_tiled::EnsembleSpan *d_span, *h_span;
+  // the constants of member m at [m] (by member, never by position in a batch), filled and copied once by the first fused round that
+  // reads them and never written again: the kernels read them through scalar loads (hip/ensemble_scan.h).  0: no such round yet
+  rgpu_tiled::MemberConst *d_tab, *h_tab;
 #endif
+  bool scan;                     // created by rgpu_ensemble_create_scan ...
+  bool uniform;                  // ... all of whose sets are bytewise equal (always true for rgpu_ensemble_create)
   std::string err;
 };
 
@@ -36,6 +44,34 @@ int ensemble_validate(const rgpu_params* p, int members, std::string* why) {
   if (p->slab_count != 1) { *why = "ensemble: a slab of a larger box (slab_count > 1) cannot be a member"; return RGPU_EUNSUPPORTED; }
   return RGPU_OK;
 }
+// what rgpu_ensemble_create_scan accepts: every set what rgpu_ensemble_create accepts, and the sets alike in everything that selects
+// code or shape -- the integers, slope_type, the sign classes of cIso, Omega0, nu and eta (what spec_matches, clock_config_ok,
+// hydro2d_images and mhd2d_images look at).  Every other double may differ from member to member
+int scan_validate(const rgpu_params* sets, int members, std::string* why) {
+  if (members < 1 || members > RGPU_ENSEMBLE_MAX_MEMBERS) { *why = "ensemble: members must be 1 .. " + std::to_string(RGPU_ENSEMBLE_MAX_MEMBERS); return RGPU_EINVAL; }
+  if (!sets) { *why = "ensemble: the array of parameter sets is NULL"; return RGPU_EINVAL; }
+  const rgpu_params& a = sets[0];
+  for (int m = 0; m < members; ++m) {
+    const rgpu_params& b = sets[m];
+    std::string w;
+    if (const int vr = ensemble_validate(&b, members, &w)) { *why = "ensemble: member " + std::to_string(m) + ": " + w; return vr; }
+    const char* field = 0;
+#define RG_SHARED(F) if (!field && a.F != b.F) field = #F;
+    RG_SHARED(abi_version) RG_SHARED(nx) RG_SHARED(ny) RG_SHARED(nz) RG_SHARED(ghostWidth) RG_SHARED(nbVar) RG_SHARED(mhdEnabled)
+    RG_SHARED(bc[0]) RG_SHARED(bc[1]) RG_SHARED(bc[2]) RG_SHARED(bc[3]) RG_SHARED(bc[4]) RG_SHARED(bc[5])
+    RG_SHARED(slope_type) RG_SHARED(niter_riemann) RG_SHARED(iorder) RG_SHARED(riemannSolver) RG_SHARED(magRiemannSolver)
+    RG_SHARED(implementationVersion) RG_SHARED(unsplitVersion) RG_SHARED(shearingBoxEnabled) RG_SHARED(enableJet) RG_SHARED(ijet) RG_SHARED(offsetJet)
+    RG_SHARED(slab_rank) RG_SHARED(slab_count) RG_SHARED(nz_global) RG_SHARED(gravityEnabled) RG_SHARED(zStratifiedFloor)
+    RG_SHARED(randomForcingEnabled) RG_SHARED(ouForcingEnabled) RG_SHARED(ouInitRandom)
+#undef RG_SHARED
+    if (field) { *why = std::string("ensemble scan: ") + field + " of member " + std::to_string(m) + " differs from member 0's: the members of a scan share every integer field and slope_type"; return RGPU_EINVAL; }
+#define RG_SIGN(F) if (!field && (a.F > 0) != (b.F > 0)) field = #F;
+    RG_SIGN(cIso) RG_SIGN(Omega0) RG_SIGN(nu) RG_SIGN(eta)
+#undef RG_SIGN
+    if (field) { *why = std::string("ensemble scan: ") + field + " of member " + std::to_string(m) + " is > 0 where member 0's is not, or the other way round: that selects other code"; return RGPU_EINVAL; }
+  }
+  return RGPU_OK;
+}
 #ifdef RGPU_TILED_ENSEMBLE2D
 // the step of this member is one fused kernel that reads the device record and leaves CFL maxima and ghost images (whatever its state
 // is at the moment: clock_ready says whether the state at hand came out of such a kernel)
@@ -45,22 +81,23 @@ bool ensemble_member_fusable(rgpu_ctx* c) {
   return hydro2d_images(c) != 0 && rgpu_tiled::hydro2d_step_covers(c->g);
 }
 #endif
-}  // namespace
 
-extern "C" {
-
-int rgpu_ensemble_create(const rgpu_params* p, int members, rgpu_ensemble** out) {
+// sets: one parameter set (!scan: every member is created from it) or `members` of them (scan)
+int ensemble_create_impl(const rgpu_params* sets, int members, bool scan, rgpu_ensemble** out) {
   if (!out) return RGPU_EINVAL;
+  const rgpu_params* p = sets;   // member 0's: the shape, shared
   *out = 0;
   rgpu_ensemble* e = new (std::nothrow) rgpu_ensemble();
   if (!e) return RGPU_ENOMEM;
   *out = e;   // returned even on failure so that rgpu_ensemble_last_error can be read; the caller destroys it
   e->members = 0; e->device = -1; e->U = 0; e->stride = 0; e->slots = 0;
 #ifdef RGPU_TILED_ENSEMBLE2D
-  e->d_clk = e->h_clk = 0; e->d_span = e->h_span = 0;
+  e->d_clk = e->h_clk = 0; e->d_span = e->h_span = 0; e->d_tab = e->h_tab = 0;
 #endif
+  e->scan = scan; e->uniform = true;
   std::string why;
-  if (const int vr = ensemble_validate(p, members, &why)) return efail(e, vr, why);
+  if (const int vr = scan ? scan_validate(sets, members, &why) : ensemble_validate(p, members, &why)) return efail(e, vr, why);
+  for (int m = 1; scan && m < members; ++m) e->uniform = e->uniform && !std::memcmp(&sets[0], &sets[m], sizeof(rgpu_params));
   if (rg_device_count() < 1) return efail(e, RGPU_ENODEVICE, "no HIP device: this library has no CPU fallback (backend " RG_BACKEND_NAME ")");
   e->device = rg_current_device();
   e->stride = ensemble_stride(*p);
@@ -71,13 +108,19 @@ int rgpu_ensemble_create(const rgpu_params* p, int members, rgpu_ensemble** out)
   e->ctx.reserve(M);
   for (size_t m = 0; m < M; ++m) {
     rgpu_ctx* c = 0;
-    const int rc = create_common(p, e->U + m * e->stride, e->U + (M + m) * e->stride, 0, true, &c, e->slots + m * 3 * RG_DT_SLOTS);
+    const int rc = create_common(scan ? &sets[m] : p, e->U + m * e->stride, e->U + (M + m) * e->stride, 0, true, &c, e->slots + m * 3 * RG_DT_SLOTS);
     if (c) { c->borrowed = true; e->ctx.push_back(c); }
     if (rc) return efail(e, rc, "ensemble: member " + std::to_string(m) + ": " + (c ? c->err : std::string("allocation failed")));
   }
   e->members = members;
   return RGPU_OK;
 }
+}  // namespace
+
+extern "C" {
+
+int rgpu_ensemble_create(const rgpu_params* p, int members, rgpu_ensemble** out) { return ensemble_create_impl(p, members, false, out); }
+int rgpu_ensemble_create_scan(const rgpu_params* sets, int members, rgpu_ensemble** out) { return ensemble_create_impl(sets, members, true, out); }
 
 void rgpu_ensemble_destroy(rgpu_ensemble* e) {
   if (!e) return;
@@ -89,9 +132,10 @@ void rgpu_ensemble_destroy(rgpu_ensemble* e) {
   }
   rg_free(e->U); rg_free(e->slots);
 #ifdef RGPU_TILED_ENSEMBLE2D
-  rg_free(e->d_clk); rg_free(e->d_span);
+  rg_free(e->d_clk); rg_free(e->d_span); rg_free(e->d_tab);
   if (e->h_clk) rg_host_free(e->h_clk);
   if (e->h_span) rg_host_free(e->h_span);
+  if (e->h_tab) rg_host_free(e->h_tab);
 #endif
   delete e;
 }
@@ -111,6 +155,16 @@ size_t rgpu_ensemble_device_bytes(const rgpu_params* p, int members) {
   per_member += (size_t)rgpu_ctx::kClockBatch * sizeof(StepClock) + sizeof(rgpu_tiled::EnsembleSpan);
 #endif
   return (size_t)members * per_member;
+}
+
+size_t rgpu_ensemble_scan_device_bytes(const rgpu_params* sets, int members) {
+  std::string why;
+  if (scan_validate(sets, members, &why)) return 0;
+  size_t n = rgpu_ensemble_device_bytes(&sets[0], members);   // (what a member allocates follows from the shared integers)
+#ifdef RGPU_TILED_ENSEMBLE2D
+  n += (size_t)members * sizeof(rgpu_tiled::MemberConst);      // the table of the fused rounds (as many again in pinned host memory)
+#endif
+  return n;
 }
 
 int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, int* nStep, double* t, double* dt, double* dt_log, int* done, int* stop, int* fused_steps) {
@@ -196,12 +250,43 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
     for (int m = 0; m < M; ++m) { e->h_span[m].t0 = 0.0; e->h_span[m].tEnd = -HUGE_VAL; }   // not in this batch: its first record says stop
     for (int m : R) { e->h_span[m].t0 = t[m]; e->h_span[m].tEnd = end_of(m); }
     if (rg_copy_h2d(e->d_span, e->h_span, (size_t)M * sizeof(rgpu_tiled::EnsembleSpan), s)) return finish(efail(e, RGPU_EHIP, std::string("ensemble_run_steps: ") + rg_last_error_string()));
+    // Constants by value (member R[0]'s, for everybody) or per member from the table: a scan whose sets differ, or any ensemble under
+    // the diagnostic option member_params.  The table holds ALL members, running or not, and is written here once for good
+    const bool use_tab = rgpu::options().member_params != 0 || (e->scan && !e->uniform);
+    if (use_tab && !e->d_tab) {
+      if (rg_malloc((void**)&e->d_tab, (size_t)M * sizeof(rgpu_tiled::MemberConst)) || (!e->h_tab && rg_host_alloc((void**)&e->h_tab, (size_t)M * sizeof(rgpu_tiled::MemberConst)))) {
+        rg_free(e->d_tab); e->d_tab = 0;   // (d_tab != 0 means "filled and copied")
+        return finish(efail(e, RGPU_ENOMEM, "ensemble_run_steps: allocation of the table of member constants failed"));
+      }
+      for (int m = 0; m < M; ++m) {
+        rgpu_ctx* c = e->ctx[(size_t)m];
+        rgpu_tiled::MemberConst& mc = e->h_tab[m];
+        std::memset(&mc, 0, sizeof(mc));
+        mc.g = c->g;
+        mc.g.hdt = 0.0; mc.g.hgx = 0.0; mc.g.hgy = 0.0; mc.g.hgz = 0.0;
+        mc.k = clock_const(c);
+        mc.rc = rot_coef(c, 0.0);
+      }
+      if (rg_copy_h2d(e->d_tab, e->h_tab, (size_t)M * sizeof(rgpu_tiled::MemberConst), s)) {
+        const std::string why = rg_last_error_string();
+        rg_free(e->d_tab); e->d_tab = 0;
+        return finish(efail(e, RGPU_EHIP, "ensemble_run_steps: copy of the table of member constants: " + why));
+      }
+    }
     rgpu_ctx* c0 = e->ctx[(size_t)R[0]];
     DevParams g = c0->g;
     g.hdt = 0.0; g.hgx = 0.0; g.hgy = 0.0; g.hgz = 0.0;   // (no gravity on this path)
     const ClockConst kc = clock_const(c0);
     const RotCoef rotc = rot_coef(c0, 0.0);
     const int images = c0->p.mhdEnabled ? 1 : hydro2d_images(c0);
+    // table path: one instantiation for all members, chosen as the by-value path chooses it; what it assumes is shared by the sets
+    // of a scan (scan_validate) -- were a member's constants ever not to satisfy it, the generic instantiation assumes nothing
+    bool mhd_plain = pick_spec(g) == 2;
+    int hydro_spec = use_tab && !c0->p.mhdEnabled ? rgpu_tiled::hydro2d_scan_spec(g) : 0;
+    for (int m = 0; use_tab && m < M; ++m) {
+      if (!spec_matches(kSpecPlain, e->ctx[(size_t)m]->g)) mhd_plain = false;
+      if (!spec_matches(hydro_spec, e->ctx[(size_t)m]->g)) hydro_spec = 0;
+    }
     unsigned long long* slots = e->slots + (size_t)phase * RG_DT_SLOTS;
     const size_t pool = (size_t)M * e->stride;
     const unsigned stride = (unsigned)e->stride;
@@ -209,13 +294,19 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
     int queued = 0, rc = 0;
     for (; queued < nb; ++queued) {
       StepClock* rec = e->d_clk + (size_t)queued * M;
-      if (rgpu_tiled::launch_ensemble_clock(s, M, slots, kc, e->d_span, queued ? rec - M : 0, rec)) { rc = -1; break; }
+      if (use_tab ? rgpu_tiled::launch_scan_clock(s, M, slots, e->d_tab, e->d_span, queued ? rec - M : 0, rec)
+                  : rgpu_tiled::launch_ensemble_clock(s, M, slots, kc, e->d_span, queued ? rec - M : 0, rec)) { rc = -1; break; }
       const int pin = (par + queued) % 2, pout = 1 - pin;
       for (int m : R) { e->ctx[(size_t)m]->rec.drop_scan(); e->ctx[(size_t)m]->rec.drop_ghosts(); }   // the output arrays are about to change
       const double* in = e->U + (size_t)pin * pool;
       double* out = e->U + (size_t)pout * pool;
-      const int rs = c0->p.mhdEnabled ? rgpu_tiled::mhd2d_ensemble_step<kSpecPlain>(s, M, g, rotc, pick_spec(g) == 2, in, out, stride, slots, images, rec)
-                                      : rgpu_tiled::hydro2d_ensemble_step(s, M, g, in, out, stride, slots, images, rec);
+      int rs;
+      if (use_tab)
+        rs = c0->p.mhdEnabled ? rgpu_tiled::mhd2d_scan_step<kSpecPlain>(s, M, g, mhd_plain, e->d_tab, in, out, stride, slots, images, rec)
+                              : rgpu_tiled::hydro2d_scan_step(s, M, g, hydro_spec, e->d_tab, in, out, stride, slots, images, rec);
+      else
+        rs = c0->p.mhdEnabled ? rgpu_tiled::mhd2d_ensemble_step<kSpecPlain>(s, M, g, rotc, pick_spec(g) == 2, in, out, stride, slots, images, rec)
+                              : rgpu_tiled::hydro2d_ensemble_step(s, M, g, in, out, stride, slots, images, rec);
       if (rs) { rc = -1; break; }
       for (int m : R) { e->ctx[(size_t)m]->rec.scanned(pout, RG_DT_SLOTS); e->ctx[(size_t)m]->rec.ghosts_written(pout); }
     }

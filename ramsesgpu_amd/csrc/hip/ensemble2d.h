@@ -11,6 +11,8 @@
 // ensemble_clock_kernel is step_clock_kernel with one workgroup per member: the same fold, the same step_clock_form, the same
 // re-zeroing rule -- one launch per step for all members.  Records are laid out tick-major (record of tick n, member m at
 // [n * members + m]) so that the host reads the records of a batch back in one contiguous copy.
+// ensemble_scan.h (included at the end): the same three kernels with DevParams / RotCoef / ClockConst per member, read from a table in
+// device memory instead of the kernel arguments -- a parameter scan (rgpu_ensemble_create_scan).
 #pragma once
 #include "tiled_hydro2d.h"
 #include "tiled_mhd2d.h"
@@ -135,3 +137,5 @@ inline int mhd2d_ensemble_step(rg_stream_t s, int members, const DevParams& g, c
 }
 
 }  // namespace rgpu_tiled
+
+#include "ensemble_scan.h"   // the same kernels with per-member constants from a device table (parameter scans)

@@ -1,5 +1,6 @@
 """An ensemble of 2D boxes on one GPU (rgpu_ensemble_*, include/rgpu.h): members of one shape and one solver configuration, each with
 its own state, dt sequence and end time, advanced by one step-kernel launch and one clock-kernel launch per step for all of them.
+`Ensemble(p, M)`: M boxes of one parameter set; `Ensemble.scan([p_0, ..])`: a parameter scan, one set per member.
 No numerics live here: `Ensemble` owns the C object, `member(m)` is a `Solver` view of one member's borrowed context."""
 import ctypes as C
 
@@ -28,17 +29,34 @@ class _Member(Solver):
 
 class Ensemble:
     def __init__(self, params, members, library=None):
+        self._create(library, [params] * max(int(members), 1), int(members), scan=False)
+
+    @classmethod
+    def scan(cls, params_list, library=None):
+        """a parameter scan (rgpu_ensemble_create_scan): member m is created from params_list[m].  The sets share every integer field,
+        slope_type and the signs of cIso, Omega0, nu and eta (what selects code or shape); every other double may differ"""
+        self = cls.__new__(cls)
+        sets = list(params_list)
+        self._create(library, sets, len(sets), scan=True)
+        return self
+
+    def _create(self, library, sets, members, scan):
         self.L = library or load_library()
         self.lib = _capi.declare_ensemble_api(self.L.lib)
-        self.p = params
+        self.p = sets[0] if sets else None
         self.ens = C.c_void_p()
-        rc = self.lib.rgpu_ensemble_create(C.byref(params), int(members), C.byref(self.ens))
+        self._sets = None
+        if scan:
+            self._sets = (_capi.RgpuParams * max(len(sets), 1))(*sets)   # kept: device_bytes() asks with the same array
+            rc = self.lib.rgpu_ensemble_create_scan(self._sets if sets else None, members, C.byref(self.ens))
+        else:
+            rc = self.lib.rgpu_ensemble_create(C.byref(self.p), members, C.byref(self.ens))
         if rc:
             msg = self.lib.rgpu_ensemble_last_error(self.ens).decode() if self.ens else "?"
             self.close()
-            raise RgpuError("rgpu_ensemble_create failed (%d): %s" % (rc, msg))
+            raise RgpuError("%s failed (%d): %s" % ("rgpu_ensemble_create_scan" if scan else "rgpu_ensemble_create", rc, msg))
         self.members = self.lib.rgpu_ensemble_members(self.ens)
-        self._views = [_Member(params, self.L, self.lib.rgpu_ensemble_member(self.ens, m)) for m in range(self.members)]
+        self._views = [_Member(sets[m], self.L, self.lib.rgpu_ensemble_member(self.ens, m)) for m in range(self.members)]
 
     def close(self):
         for v in getattr(self, "_views", []):
@@ -62,6 +80,8 @@ class Ensemble:
         return self._views[m]
 
     def device_bytes(self):
+        if self._sets is not None:
+            return int(self.lib.rgpu_ensemble_scan_device_bytes(self._sets, self.members))
         return int(self.lib.rgpu_ensemble_device_bytes(C.byref(self.p), self.members))
 
     def start(self, U0s):

@@ -9,6 +9,14 @@ same alternation: (a), (b), (b on the baseline) take turns in one process, `--re
 (--window seconds, steps calibrated per mode) and ended by a device synchronise.  Numbers are cell updates per second of the WHOLE CALL
 (host loop, launches, read-backs included) -- not a kernel's share of peak.  Needs a GPU: there is no fallback.
 
+Parameter scans (rgpu_ensemble_create_scan: one parameter set per member, the members' constants read from a table on the device):
+  --member-params   adds (a'): the same equal boxes as (a) with the library option member_params = 1, i.e. the uniform ensemble
+                    through the table kernels -- the A/B of the table path against the by-value path; with --baseline-lib also (a) on
+                    the baseline build, when that build has the ensemble
+  --scan gamma0     adds (s): M boxes whose gamma0 is spread evenly over +-10 % of the ini value, as ONE scan ensemble, and (b_s):
+                    the same M parameter sets as M lone contexts stepped one after another (no new API: with --baseline-lib also on
+                    the baseline build, which is the column the acceptance of DESIGN 3.6.1 is phrased against)
+
 --single-box (with --baseline-lib) adds (c): ONE box stepped with rgpu_run_steps on this build and on the baseline build, taking turns,
 for the 2D step kernels whose bodies the ensemble shares -- Orszag-Tang, Kelvin-Helmholtz and Rayleigh-Taylor (uniform gravity: its
 instantiation of the hydro kernel is the one whose register count moved) at --single-size."""
@@ -33,25 +41,41 @@ def ini(base):
     return os.path.join(ROOT, "configs", base + ".ini")
 
 
-def member_states(lib, base, ov, p, members):
-    """the initial condition with a seeded 1e-3 perturbation of density and momenta per member (tests/ensemble_checks.py)"""
+def member_state(lib, base, ov, p, m):
+    """the initial condition with a seeded 1e-3 perturbation of density and momenta for member m (tests/ensemble_checks.py)"""
     U0 = lib.init_condition(ini(base), ov, p)
+    rng = np.random.default_rng(7000 + m)
+    U = U0.copy()
+    U[0] *= 1.0 + 1e-3 * rng.uniform(-1.0, 1.0, U[0].shape)
+    for v in (2, 3):
+        U[v] += 1e-3 * rng.uniform(-1.0, 1.0, U[v].shape) * U0[0]
+    return U
+
+
+def member_states(lib, base, ov, p, members):
+    return [member_state(lib, base, ov, p, m) for m in range(members)]
+
+
+def scan_sets(lib, base, ov, key, members):
+    """(s): per member (overrides, parameter set) with `key` (an ini key of section hydro, e.g. gamma0) spread evenly over +-10 % of the ini
+    value, in an order that is not monotonic in the member index"""
+    v0 = getattr(lib.params_from_ini(ini(base), ov), key)
+    order = sorted(range(members), key=lambda m: (m * 37) % members if members > 1 else 0)
     out = []
     for m in range(members):
-        rng = np.random.default_rng(7000 + m)
-        U = U0.copy()
-        U[0] *= 1.0 + 1e-3 * rng.uniform(-1.0, 1.0, U[0].shape)
-        for v in (2, 3):
-            U[v] += 1e-3 * rng.uniform(-1.0, 1.0, U[v].shape) * U0[0]
-        out.append(U)
+        v = v0 * (0.9 + 0.2 * (order[m] / (members - 1) if members > 1 else 0.5))
+        o = "%s;hydro.%s=%.17g" % (ov, key, v)
+        out.append((o, lib.params_from_ini(ini(base), o)))
     return out
 
 
 class Replicas:
-    """mode (b): M contexts, stepped one after another"""
+    """mode (b) / (b_s): M contexts, stepped one after another; ps: one parameter set for all, or one per context"""
 
-    def __init__(self, lib, p, U0s):
-        self.solvers = [Solver(p, lib) for _ in U0s]
+    def __init__(self, lib, ps, U0s):
+        if not isinstance(ps, (list, tuple)):
+            ps = [ps] * len(U0s)
+        self.solvers = [Solver(p, lib) for p in ps]
         for sv, U in zip(self.solvers, U0s):
             sv.start(U, 0)
 
@@ -67,16 +91,24 @@ class Replicas:
 
 
 class OneEnsemble:
-    """mode (a)"""
+    """mode (a); member_params: (a'), the library option set around every call; ps a list: (s), a scan ensemble"""
 
-    def __init__(self, lib, p, U0s):
+    def __init__(self, lib, ps, U0s, member_params=False):
         from ramsesgpu_amd.ensemble import Ensemble
-        self.ens = Ensemble(p, len(U0s), lib)
+        self.lib, self.member_params = lib, member_params
+        self.ens = Ensemble.scan(ps, lib) if isinstance(ps, (list, tuple)) else Ensemble(ps, len(U0s), lib)
         self.ens.start(U0s)
         self.fused = 0
 
     def run(self, k):
-        done, stop, fused = self.ens.run_steps(k)
+        if self.member_params:
+            old = self.lib.set_option("member_params", 1)
+            try:
+                done, stop, fused = self.ens.run_steps(k)
+            finally:
+                self.lib.set_option("member_params", old)
+        else:
+            done, stop, fused = self.ens.run_steps(k)
         if min(done) != k:
             raise RuntimeError("ensemble member stopped early: %s %s" % (done, stop))
         self.fused += fused
@@ -114,6 +146,9 @@ def main():
     ap.add_argument("--window", type=float, default=0.7, help="seconds per timed window (well above 0.5)")
     ap.add_argument("--single-box", action="store_true", help="(c): one box, this build against --baseline-lib, taking turns")
     ap.add_argument("--single-size", type=int, default=512)
+    ap.add_argument("--member-params", action="store_true", help="(a'): the equal boxes of (a) with option member_params = 1 (the table kernels)")
+    ap.add_argument("--scan", default=None, metavar="KEY", help="(s) / (b_s): M boxes with hydro.KEY (gamma0) spread over +-10 %% of the ini value")
+    ap.add_argument("--no-replicas", action="store_true", help="leave out (b), the equal boxes as lone contexts (profiles/ensemble_bench.json has it)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lib = Library(lib_path(a.arith))
@@ -123,6 +158,8 @@ def main():
         have_ensemble = True
     except ImportError:
         have_ensemble = False
+    have_scan = have_ensemble and hasattr(ramsesgpu_amd.ensemble.Ensemble, "scan")
+    base_has_ensemble = bool(base_lib) and hasattr(base_lib.lib, "rgpu_ensemble_create")
     rows = []
     for w in a.workloads.split(","):
         for size in (int(s) for s in a.sizes.split(",")):
@@ -133,9 +170,22 @@ def main():
                 modes = {}
                 if have_ensemble:
                     modes["a_ensemble"] = OneEnsemble(lib, p, U0s)
-                modes["b_replicas"] = Replicas(lib, p, U0s)
-                if base_lib:
-                    modes["b_replicas_baseline"] = Replicas(base_lib, base_lib.params_from_ini(ini(WORKLOADS[w]), ov), U0s)
+                if not a.no_replicas:
+                    modes["b_replicas"] = Replicas(lib, p, U0s)
+                    if base_lib:
+                        modes["b_replicas_baseline"] = Replicas(base_lib, base_lib.params_from_ini(ini(WORKLOADS[w]), ov), U0s)
+                if a.member_params and have_scan:
+                    modes["a_member_params"] = OneEnsemble(lib, p, U0s, member_params=True)
+                    if base_has_ensemble:
+                        modes["a_ensemble_baseline"] = OneEnsemble(base_lib, base_lib.params_from_ini(ini(WORKLOADS[w]), ov), U0s)
+                if a.scan:
+                    sets = scan_sets(lib, WORKLOADS[w], ov, a.scan, M)
+                    Us = [member_state(lib, WORKLOADS[w], o, q, m) for m, (o, q) in enumerate(sets)]   # each set's own initial condition
+                    if have_scan:
+                        modes["s_scan"] = OneEnsemble(lib, [q for _, q in sets], Us)
+                    modes["bs_scan_replicas"] = Replicas(lib, [q for _, q in sets], Us)
+                    if base_lib:
+                        modes["bs_scan_replicas_baseline"] = Replicas(base_lib, [base_lib.params_from_ini(ini(WORKLOADS[w]), o) for o, _ in sets], Us)
                 steps = {name: calibrate(mode, a.window) for name, mode in modes.items()}
                 rates = {name: [] for name in modes}
                 secs = {name: [] for name in modes}
@@ -148,8 +198,11 @@ def main():
                 for name in modes:
                     r = rates[name]
                     row[name] = {"median": statistics.median(r), "min": min(r), "max": max(r), "steps_per_window": steps[name], "window_s_min": min(secs[name]), "repeats": len(r)}
-                if have_ensemble:
-                    row["a_ensemble"]["fused_rounds"] = modes["a_ensemble"].fused
+                for name, mode in modes.items():
+                    if isinstance(mode, OneEnsemble):
+                        row[name]["fused_rounds"] = mode.fused
+                if a.scan:
+                    row["scan"] = {"key": a.scan, "values": [getattr(q, a.scan) for _, q in sets]}
                 for mode in modes.values():
                     mode.close()
                 rows.append(row)
