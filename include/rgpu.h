@@ -432,7 +432,7 @@ int rgpu_clock_check(rgpu_ctx* c);
  *   rgpu_ensemble_run_steps gives member m exactly what rgpu_run_steps_log gives a lone context created from sets[m] (bit for bit in
  *   librgpu.so, relative L2 <= 1e-12 in librgpu_fast.so).  On the fused rounds every workgroup reads its member's constants
  *   (DevParams, the clock's constants, the rotating-frame coefficients: 384 bytes per member) from a table in device memory through
- *   scalar loads (csrc/hip/ensemble_scan.h) instead of the kernel arguments; the table is written once, by the first fused round, and
+ *   scalar loads (csrc/hip/ensemble_scan.h) instead of the kernel arguments; the table is written once, by the first fused round (or rgpu_ensemble_monitor), and
  *   never again.  The same kernel bodies, the same placement on a CU as the uniform ensemble kernels in every instantiation (DESIGN
  *   3.6.1: no retreat was needed for the generic 2D MHD kernel).  A scan whose sets are all bytewise equal takes the by-value
  *   launch of rgpu_ensemble_create (unless option "member_params" is 1).  Where a configuration is off the fused path it is so for
@@ -452,6 +452,73 @@ size_t rgpu_ensemble_scan_device_bytes(const rgpu_params* sets, int members);
 const char* rgpu_ensemble_last_error(rgpu_ensemble* e);
 int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, int* nStep, double* t, double* dt, double* dt_log, int* done,
                             int* stop, int* fused_steps);
+
+/* ---- monitors: per-member totals and extrema, reduced on the device --------------------------------------------------------------
+ * What a user wants out of a run of 64 seeds or of a parameter scan is a time series per member; downloading every member's state
+ * for it (64 members of 128^2, 8 variables: 67 MB per sample) would end the batch of queued rounds an ensemble exists for.  A monitor
+ * is RGPU_MON_NQ = 10 doubles of a 2D state U[parity], hydro or MHD, taken over its nx x ny INTERIOR cells and raw (not multiplied by
+ * dx dy):
+ *     q  0 mass   1 mx   2 my   3 mz   4 E   5 ekin   6 emag        sums
+ *        7 min_rho   8 min_eint                                     minima
+ *        9 max_absdivb                                              maximum
+ * Per-cell terms, with IEEE + - * / in exactly this order and no FMA contraction in either library (csrc/kernels_monitor.h):
+ *     rho = U[ID], E = U[IP], mx = U[IU], my = U[IV], mz = U[IW] (hydro, nbVar == 4: +0.0)
+ *     ekin = (0.5 * ((mx * mx + my * my) + mz * mz)) / rho
+ *     MHD:   bxc = 0.5 * (Bx(i,j) + Bx(i+1,j)), byc = 0.5 * (By(i,j) + By(i,j+1)), bzc = U[IC],
+ *            emag = 0.5 * ((bxc * bxc + byc * byc) + bzc * bzc),
+ *            absdivb = | (Bx(i+1,j) - Bx(i,j)) / dx + (By(i,j+1) - By(i,j)) / dy |       (dx, dy: the context's own)
+ *     hydro: emag = +0.0, absdivb = +0.0            (columns 3, 6 and 9 of a hydro state are exactly 0)
+ *     eint = (E - ekin) - emag
+ *   The high faces of the last interior row and column lie in the first ghost layer; they hold their constrained-transport value
+ *   after every step and after a ghost fill, so no ghost fill is done (rgpu_history_* read the same faces).
+ * Summation order: fixed by (nx, ny), RGPU_MON_ROWS and RGPU_MON_LANES alone -- not by the number of members, the member index,
+ * the position in a batch, fused or member-by-member rounds, the by-value or table path, or the library.  No floating-point
+ * atomics.  With ii = i - ghostWidth in [0, nx), jj = j - ghostWidth in [0, ny), every accumulator starting at +0.0 and taking
+ * "a = a + x" in the order given:
+ *     1. P[s][ii] = sum of the terms of column ii over jj = s * ROWS .. min(ny, (s + 1) * ROWS) - 1, ascending   (s < nseg = ceil(ny / ROWS))
+ *     2. C[ii]    = sum of P[s][ii] over s = 0 .. nseg - 1, ascending
+ *     3. L[l]     = sum of C[ii] over ii = l, l + LANES, l + 2 LANES, .. < nx, ascending                          (l < LANES; no such ii: +0.0)
+ *     4. for off = LANES / 2, LANES / 4, .., 1:  L[l] <- L[l] + L[l ^ off] for all l at once;  the sum is L[0]
+ *   (tests/monitor_checks.py is this order in numpy and reproduces every double.)  Whatever the order, |S - exact| <= N 2^-53 sum |terms|.
+ * Extrema: fmin from +inf, fmax from +0.0 along the same route, order-free.  NaN: a NaN in a state propagates into the sums that
+ * contain it as IEEE addition does; fmin / fmax return their other operand when one is NaN, so the extrema are those of the cells
+ * whose term is a number (all terms NaN: +inf / +0.0 stay).  Members do not see each other: a poisoned member changes no other's values.
+ *
+ *   rgpu_state_monitor     out[RGPU_MON_NQ] of U[parity] of any 2D context, in any configuration (3D: RGPU_EUNSUPPORTED).  Reads the
+ *                          state only: ghost cells, CFL slots and what the context knows about them stay as they are.  Synchronises.
+ *   rgpu_ensemble_monitor  out[members][RGPU_MON_NQ] of every member's CURRENT state -- U[0] after rgpu_upload, U[nStep % 2] after steps
+ *                          taken through rgpu_one_step_integration / rgpu_godunov_unsplit / rgpu_run_steps* on the member or
+ *                          rgpu_ensemble_run_steps* -- with two launches for all members and one read-back.  The staged entry points
+ *                          (rgpu_step_pre / _core / _post_*, the plane-ranged pieces, rgpu_clock_*) do NOT move what counts as a
+ *                          member's current state: a caller that drives a member through them reads it with rgpu_state_monitor
+ *                          and the parity it knows.
+ *   rgpu_ensemble_run_steps_monitored   rgpu_ensemble_run_steps (same arguments, same states, dt sequences, done, stop, fused_steps) plus
+ *                          sampling: member m is sampled after each of its steps that brings nStep[m] to a multiple of `every` -- its
+ *                          own global step number, so the series does not depend on how a run is cut into calls and members with
+ *                          different nStep are sampled at different rounds.  mon_n[m] = its samples in this call (<= cap = nsteps /
+ *                          every + 1); sample k of member m: mon_step[m * cap + k] the step number, mon_t[m * cap + k] the
+ *                          host-accumulated t[m] after that step (the double the loop returns), mon[(m * cap + k) * RGPU_MON_NQ + q] the
+ *                          values.  A member that stops on reaching its tEnd is sampled if its last step qualifies; a member stopped
+ *                          with code 2 or 3 gets no further samples.  every < 1 or a null monitor pointer: RGPU_EINVAL.
+ *                          On fused rounds the host queues the monitor kernels (csrc/hip/ensemble_monitor.h) behind the step launch of
+ *                          every round after which some running member qualifies; each workgroup decides from its member's clock record
+ *                          and step number whether to sample; the values go to a device log that is copied back once per batch
+ *                          with the clock records: no synchronisation inside a batch.  On member-by-member rounds the loop is cut at
+ *                          the member's next sampling step and rgpu_state_monitor is called on its context (one synchronisation per
+ *                          sample).  Both give the doubles of rgpu_state_monitor on a lone context holding that state.
+ *   rgpu_ensemble_monitor_device_bytes   the extra device memory, allocated by the first call that samples on the device (per member:
+ *                          the segment sums, RGPU_CLOCK_BATCH log slots, 8 bytes of bookkeeping; the log as many again in pinned host
+ *                          memory).  rgpu_ensemble_device_bytes / _scan_device_bytes do not include it.  0 for refused parameters. */
+#define RGPU_MON_NQ 10
+#define RGPU_MON_ROWS 32    /* rows per segment of the summation order */
+#define RGPU_MON_LANES 64   /* lanes of the summation order (one wavefront) */
+int rgpu_state_monitor(rgpu_ctx* c, int parity, double* out /* [RGPU_MON_NQ] */);
+int rgpu_ensemble_monitor(rgpu_ensemble* e, double* out /* [members][RGPU_MON_NQ] */);
+int rgpu_ensemble_run_steps_monitored(rgpu_ensemble* e, int nsteps, const double* tEnd, int* nStep, double* t, double* dt,
+                                      double* dt_log, int* done, int* stop, int* fused_steps,
+                                      int every, int* mon_n /* [members] */, int* mon_step /* [members][cap] */,
+                                      double* mon_t /* [members][cap] */, double* mon /* [members][cap][RGPU_MON_NQ] */);
+size_t rgpu_ensemble_monitor_device_bytes(const rgpu_params* p, int members);
 
 /* Self-test of the device arithmetic the parity contract rests on: for n operand pairs computes on the device
  *   quot[i]  = rg_div(num[i], rg_recip(den[i]))   the shared-reciprocal division of csrc/hip/rg_backend.h

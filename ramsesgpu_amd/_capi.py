@@ -7,6 +7,9 @@ ID, IP, IU, IV, IW, IA, IB, IC = range(8)
 BC_UNDEFINED, BC_DIRICHLET, BC_NEUMANN, BC_PERIODIC, BC_SHEARINGBOX, BC_COPY, BC_Z_STRATIFIED = range(7)
 RS_APPROX, RS_HLL, RS_HLLC, RS_HLLD, RS_LLF = range(5)
 XDIR, YDIR, ZDIR = 1, 2, 3
+# the columns of a monitor (rgpu_state_monitor, rgpu_ensemble_monitor, rgpu_ensemble_run_steps_monitored): RGPU_MON_NQ = 10
+MON_NAMES = ("mass", "mx", "my", "mz", "E", "ekin", "emag", "min_rho", "min_eint", "max_absdivb")
+MON_NQ = len(MON_NAMES)
 T_NAMES = ["boundaries", "prim", "elec", "trace", "flux", "emf", "update", "shear", "dt", "dissipative", "sweep"]
 
 
@@ -201,6 +204,8 @@ def declare_device_api(lib):
     lib.rgpu_get_option.argtypes = [C.c_char_p]
     lib.rgpu_clock_check.restype = C.c_int
     lib.rgpu_clock_check.argtypes = [ctx]
+    lib.rgpu_state_monitor.restype = C.c_int
+    lib.rgpu_state_monitor.argtypes = [ctx, C.c_int, c_double_p]
     return lib
 
 
@@ -228,6 +233,13 @@ def declare_ensemble_api(lib):
     lib.rgpu_ensemble_last_error.argtypes = [ens]
     lib.rgpu_ensemble_run_steps.restype = C.c_int
     lib.rgpu_ensemble_run_steps.argtypes = [ens, C.c_int, c_double_p, int_p, c_double_p, c_double_p, c_double_p, int_p, int_p, int_p]
+    lib.rgpu_ensemble_monitor.restype = C.c_int
+    lib.rgpu_ensemble_monitor.argtypes = [ens, c_double_p]
+    lib.rgpu_ensemble_run_steps_monitored.restype = C.c_int
+    lib.rgpu_ensemble_run_steps_monitored.argtypes = [ens, C.c_int, c_double_p, int_p, c_double_p, c_double_p, c_double_p, int_p, int_p, int_p,
+                                                      C.c_int, int_p, int_p, c_double_p, c_double_p]
+    lib.rgpu_ensemble_monitor_device_bytes.restype = C.c_size_t
+    lib.rgpu_ensemble_monitor_device_bytes.argtypes = [P, C.c_int]
     return lib
 
 
@@ -242,4 +254,5 @@ DECLARED_SYMBOLS = [
     "rgpu_backend_name", "rgpu_arithmetic", "rgpu_selftest_arith", "rgpu_selftest_alfven", "rgpu_step_ou_forcing", "rgpu_ou_forcing_state", "rgpu_ou_forcing_get_state", "rgpu_ou_forcing_set_state", "rgpuh_params_from_ini", "rgpuh_run_settings", "rgpuh_init_condition", "rgpuh_init_gravity", "rgpu_set_gravity_field", "rgpuh_init_forcing", "rgpu_set_forcing_field", "rgpu_forcing_sums", "rgpu_add_forcing", "rgpuh_run", "rgpuh_run_hooked",
     "rgpu_ensemble_create", "rgpu_ensemble_destroy", "rgpu_ensemble_members", "rgpu_ensemble_member", "rgpu_ensemble_device_bytes", "rgpu_ensemble_last_error", "rgpu_ensemble_run_steps",
     "rgpu_ensemble_create_scan", "rgpu_ensemble_scan_device_bytes",
+    "rgpu_state_monitor", "rgpu_ensemble_monitor", "rgpu_ensemble_run_steps_monitored", "rgpu_ensemble_monitor_device_bytes",
 ]

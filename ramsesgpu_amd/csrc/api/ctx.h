@@ -69,6 +69,9 @@ struct rgpu_ctx {
   unsigned long long* d_red_base;   // 3 x RG_DT_SLOTS
   bool fold_mode, fold_pending; int fold_phase0; ClockFold fold;
   bool fold_request;            // set by rgpu_run_steps_log around its own rgpu_clock_open (clock_ready holds there): a batch opened from outside never folds
+  int cur;                      // parity of the array that holds the current state: 0 after rgpu_upload, (nStep + 1) % 2 after a step taken through
+                                // rgpu_godunov_unsplit / rgpu_one_step_integration, nStep % 2 after rgpu_run_steps* (what rgpu_ensemble_monitor reports; the staged
+                                // rgpu_step_* pieces do not move it: include/rgpu.h says so)
   bool borrowed;                // member of an rgpu_ensemble (api/entry_ensemble.h): state and slot arrays are slices of the ensemble's, rgpu_destroy refuses
   std::string err;
 };
@@ -243,6 +246,7 @@ int create_common(const rgpu_params* p, double* dU, double* dU2, void* hip_strea
   if (p) c->p = *p;
   c->own_state = !external;
   c->borrowed = false;
+  c->cur = 0;
   c->U[0] = c->U[1] = 0;
   c->Q = c->E = c->T = c->F = c->emf = c->shear_save = c->shear_remap = 0;
   c->G = 0;

@@ -141,6 +141,8 @@ int rgpu_clock_close(rgpu_ctx* c, int nStep0, int* ran, double* t, double* dt_la
 static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int* why) {
   *why = 0;
   int done = 0;
+  struct Current { rgpu_ctx* c; const int* n; ~Current() { c->cur = *n & 1; } } current = {c, nStep};   // however the loop is left: U[*nStep % 2] is the state
+  (void)current;
   while (done < nsteps && *t < tEnd) {
     const int parity = *nStep % 2;
     if (!clock_ready(c, parity)) {   // the reference's loop body (the first step of a run always comes through here)

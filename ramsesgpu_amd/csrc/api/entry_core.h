@@ -47,6 +47,7 @@ int rgpu_upload(rgpu_ctx* c, const double* hU, int both) {
   if (rg_copy_h2d(c->U[0], hU, bytes, c->stream)) return RG_HIPFAIL(c, "upload");
   if (both && rg_copy_d2d(c->U[1], c->U[0], bytes, c->stream)) return RG_HIPFAIL(c, "upload (copy to U2)");
   if (rg_stream_sync(c->stream)) return RG_HIPFAIL(c, "upload sync");
+  c->cur = 0;
   return RGPU_OK;
 }
 
@@ -334,6 +335,15 @@ int rgpu_state_checksum(rgpu_ctx* c, int parity, unsigned long long* out) {
   return RGPU_OK;
 }
 
+int rgpu_state_monitor(rgpu_ctx* c, int parity, double* out) {
+  RG_CHECK_CTX(c);
+  if (!out || !c->U[0]) return fail(c, RGPU_EINVAL, "state_monitor: null pointer / context without state");
+  if (c->g.three_d) return fail(c, RGPU_EUNSUPPORTED, "state_monitor: 2D contexts only (3D runs have rgpu_history_*)");
+  if (!c->F || monitor_scratch_doubles(c->g) > (size_t)c->g.fN * plan_for(c->p).f) return fail(c, RGPU_EINVAL, "state_monitor: no scratch for the segment sums");
+  if (state_monitor(c, parity, out)) return RG_HIPFAIL(c, "state_monitor");
+  return RGPU_OK;
+}
+
 double rgpu_compute_dt(rgpu_ctx* c, int useU) {
   double v = 0;
   if (!c || rgpu_compute_inv_dt(c, useU, &v) != RGPU_OK) return std::numeric_limits<double>::quiet_NaN();
@@ -420,6 +430,7 @@ int rgpu_godunov_unsplit(rgpu_ctx* c, int nStep, double dt, double totalTime) {
   if (step_pre(c, nStep) || step_core(c, nStep, dt, totalTime) || step_dissipative(c, nStep, dt, totalTime) ||
       step_forcing(c, nStep, dt) || step_ou_forcing(c, (nStep + 1) % 2, dt) || step_post_a(c, nStep, dt, totalTime) || step_post_b(c, nStep))
     return RG_HIPFAIL(c, "godunov_unsplit");
+  c->cur = (nStep + 1) & 1;
   return RGPU_OK;
 }
 

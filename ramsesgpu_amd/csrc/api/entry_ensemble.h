@@ -6,6 +6,9 @@
 // A parameter scan (rgpu_ensemble_create_scan) is the same object with one parameter set per member: the sets share what selects code
 // or shape (scan_validate), each member context is created from its own set, and the fused rounds read every member's constants from
 // a table on the device (hip/ensemble_scan.h) instead of handing one member's to the kernels by value.
+// Monitors (kernels_monitor.h): rgpu_ensemble_run_steps_monitored is the same loop with per-member samples of the ten monitor
+// quantities -- on the fused rounds taken by a kernel pair queued inside the batch (hip/ensemble_monitor.h) and read back with the
+// clock records, on the member-by-member rounds by the flat monitor of the member's context.
 #pragma once
 
 struct rgpu_ensemble {
@@ -17,9 +20,15 @@ struct rgpu_ensemble {
 #ifdef RGPU_TILED_ENSEMBLE2D
   StepClock *d_clk, *h_clk;      // records of a batch, tick-major: tick n of member m at [n * members + m]
   rgpu_tiled::EnsembleSpan *d_span, *h_span;
-  // the constants of member m at [m] (by member, never by position in a batch), filled and copied once by the first fused round that
-  // reads them and never written again: the kernels read them through scalar loads (hip/ensemble_scan.h).  0: no such round yet
+  // the constants of member m at [m] (by member, never by position in a batch), filled and copied once (ensemble_table) by the first
+  // caller that reads them -- a fused round, or rgpu_ensemble_monitor outside any round, on the ensemble's stream before the kernels
+  // that read it -- and never written again: the kernels read them through scalar loads (hip/ensemble_scan.h).  0: not yet
   rgpu_tiled::MemberConst *d_tab, *h_tab;
+  // monitors, allocated by the first call that samples on the device: per member and batch its step number at the start (and, outside
+  // a batch, the parity of its state); the segment sums of one launch; the log of a batch, slot (launch, m) -- the log as many again
+  // in pinned host memory
+  rgpu_tiled::MonitorSpan *d_mspan, *h_mspan;
+  double *d_mpart, *d_mlog, *h_mlog;
 #endif
   bool scan;                     // created by rgpu_ensemble_create_scan ...
   bool uniform;                  // ... all of whose sets are bytewise equal (always true for rgpu_ensemble_create)
@@ -80,6 +89,49 @@ bool ensemble_member_fusable(rgpu_ctx* c) {
   if (c->p.mhdEnabled) return mhd2d_images(c) && rgpu_tiled::mhd2d_step_covers(c->g);
   return hydro2d_images(c) != 0 && rgpu_tiled::hydro2d_step_covers(c->g);
 }
+
+// The table of member constants (hip/ensemble_scan.h) on the device: ALL members, running or not, filled and copied once for good by
+// the first caller that needs it.  Returns RGPU_OK or a code with the message in e->err
+int ensemble_table(rgpu_ensemble* e, rg_stream_t s, const char* who) {
+  if (e->d_tab) return RGPU_OK;
+  const int M = e->members;
+  if (rg_malloc((void**)&e->d_tab, (size_t)M * sizeof(rgpu_tiled::MemberConst)) || (!e->h_tab && rg_host_alloc((void**)&e->h_tab, (size_t)M * sizeof(rgpu_tiled::MemberConst)))) {
+    rg_free(e->d_tab); e->d_tab = 0;   // (d_tab != 0 means "filled and copied")
+    return efail(e, RGPU_ENOMEM, std::string(who) + ": allocation of the table of member constants failed");
+  }
+  for (int m = 0; m < M; ++m) {
+    rgpu_ctx* c = e->ctx[(size_t)m];
+    rgpu_tiled::MemberConst& mc = e->h_tab[m];
+    std::memset(&mc, 0, sizeof(mc));
+    mc.g = c->g;
+    mc.g.hdt = 0.0; mc.g.hgx = 0.0; mc.g.hgy = 0.0; mc.g.hgz = 0.0;
+    mc.k = clock_const(c);
+    mc.rc = rot_coef(c, 0.0);
+  }
+  if (rg_copy_h2d(e->d_tab, e->h_tab, (size_t)M * sizeof(rgpu_tiled::MemberConst), s)) {
+    const std::string why = rg_last_error_string();
+    rg_free(e->d_tab); e->d_tab = 0;
+    return efail(e, RGPU_EHIP, std::string(who) + ": copy of the table of member constants: " + why);
+  }
+  return RGPU_OK;
+}
+bool ensemble_uses_table(const rgpu_ensemble* e) { return rgpu::options().member_params != 0 || (e->scan && !e->uniform); }
+size_t monitor_part_doubles(const rgpu_params& p) { return (size_t)MON_NQ * (size_t)mon_nseg(p.ny) * (size_t)p.nx; }
+// the buffers of the device monitor (see struct rgpu_ensemble)
+int ensemble_monitor_buffers(rgpu_ensemble* e, const char* who) {
+  if (e->d_mlog) return RGPU_OK;
+  const size_t M = (size_t)e->members, nlog = (size_t)rgpu_ctx::kClockBatch * M * MON_NQ;
+  if (rg_malloc((void**)&e->d_mspan, M * sizeof(rgpu_tiled::MonitorSpan)) || rg_host_alloc((void**)&e->h_mspan, M * sizeof(rgpu_tiled::MonitorSpan)) ||
+      rg_malloc((void**)&e->d_mpart, M * monitor_part_doubles(e->ctx[0]->p) * sizeof(double)) || rg_host_alloc((void**)&e->h_mlog, nlog * sizeof(double)) ||
+      rg_malloc((void**)&e->d_mlog, nlog * sizeof(double))) {
+    rg_free(e->d_mlog); e->d_mlog = 0;   // (d_mlog != 0 means "all five are there"; the others are freed by rgpu_ensemble_destroy or reused)
+    rg_free(e->d_mspan); e->d_mspan = 0; rg_free(e->d_mpart); e->d_mpart = 0;
+    if (e->h_mspan) { rg_host_free(e->h_mspan); e->h_mspan = 0; }
+    if (e->h_mlog) { rg_host_free(e->h_mlog); e->h_mlog = 0; }
+    return efail(e, RGPU_ENOMEM, std::string(who) + ": allocation of the monitor buffers failed");
+  }
+  return RGPU_OK;
+}
 #endif
 
 // sets: one parameter set (!scan: every member is created from it) or `members` of them (scan)
@@ -93,6 +145,7 @@ int ensemble_create_impl(const rgpu_params* sets, int members, bool scan, rgpu_e
   e->members = 0; e->device = -1; e->U = 0; e->stride = 0; e->slots = 0;
 #ifdef RGPU_TILED_ENSEMBLE2D
   e->d_clk = e->h_clk = 0; e->d_span = e->h_span = 0; e->d_tab = e->h_tab = 0;
+  e->d_mspan = e->h_mspan = 0; e->d_mpart = e->d_mlog = e->h_mlog = 0;
 #endif
   e->scan = scan; e->uniform = true;
   std::string why;
@@ -136,6 +189,9 @@ void rgpu_ensemble_destroy(rgpu_ensemble* e) {
   if (e->h_clk) rg_host_free(e->h_clk);
   if (e->h_span) rg_host_free(e->h_span);
   if (e->h_tab) rg_host_free(e->h_tab);
+  rg_free(e->d_mspan); rg_free(e->d_mpart); rg_free(e->d_mlog);
+  if (e->h_mspan) rg_host_free(e->h_mspan);
+  if (e->h_mlog) rg_host_free(e->h_mlog);
 #endif
   delete e;
 }
@@ -167,12 +223,26 @@ size_t rgpu_ensemble_scan_device_bytes(const rgpu_params* sets, int members) {
   return n;
 }
 
-int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, int* nStep, double* t, double* dt, double* dt_log, int* done, int* stop, int* fused_steps) {
-  if (!e) return RGPU_EINVAL;
-  if (e->members < 1) return efail(e, RGPU_EINVAL, "ensemble_run_steps: the ensemble was not created");
-  if (!nStep || !t || !dt || !done) return efail(e, RGPU_EINVAL, "ensemble_run_steps: null pointer");
+}  // extern "C"
+
+namespace {
+// where rgpu_ensemble_run_steps_monitored leaves its samples (0: rgpu_ensemble_run_steps, no sampling)
+struct EnsembleMon { int every, cap; int* n; int* step; double* t; double* values; };
+
+// rgpu_ensemble_run_steps (mon == 0: exactly its launches) and rgpu_ensemble_run_steps_monitored
+int ensemble_run_impl(rgpu_ensemble* e, int nsteps, const double* tEnd, int* nStep, double* t, double* dt, double* dt_log, int* done, int* stop, int* fused_steps,
+                      const EnsembleMon* mon) {
   rg_set_device(e->device);
   const int M = e->members;
+  // sample k of member m: its step number, its t after that step, the ten values
+  auto put = [&](int m, int step, double tm, const double* v) {
+    const int k = mon->n[m];
+    if (k >= mon->cap) return;   // (cannot happen: at most nsteps / every + 1 multiples of every in nsteps consecutive step numbers)
+    mon->step[(size_t)m * mon->cap + k] = step;
+    mon->t[(size_t)m * mon->cap + k] = tm;
+    std::memcpy(mon->values + ((size_t)m * mon->cap + k) * MON_NQ, v, MON_NQ * sizeof(double));
+    mon->n[m] = k + 1;
+  };
   std::vector<int> code((size_t)M, 0);      // why member m left the loop before its nsteps were done: 0 = it did not, or 1 / 2 / 3 of its record
   std::vector<char> halted((size_t)M, 0);
   for (int m = 0; m < M; ++m) done[m] = 0;
@@ -185,7 +255,7 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
     return rc;
   };
   // up to k steps of member m alone: the single-context loop, device clock and all
-  auto alone = [&](int m, int k) -> int {
+  auto alone_plain = [&](int m, int k) -> int {
     rgpu_ctx* c = e->ctx[(size_t)m];
     const int n0 = nStep[m];
     int why = 0;
@@ -205,7 +275,24 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
     if (r < 0 && why < 2) return efail(e, r, "ensemble_run_steps: member " + std::to_string(m) + ": " + c->err);
     return 0;
   };
-  std::vector<int> R;
+  // ... sampled: cut at the member's next sampling step, the sample taken by the flat monitor of its context (one synchronisation
+  // per sample on this path)
+  auto alone = [&](int m, int k) -> int {
+    if (!mon) return alone_plain(m, k);
+    while (k > 0 && running(m)) {
+      const int to_next = mon->every - nStep[m] % mon->every, kk = k < to_next ? k : to_next, n0 = nStep[m];
+      if (const int rc = alone_plain(m, kk)) return rc;
+      if (nStep[m] > n0 && nStep[m] % mon->every == 0 && code[m] < 2) {
+        double v[MON_NQ];
+        rgpu_ctx* c = e->ctx[(size_t)m];
+        if (const int rc = rgpu_state_monitor(c, nStep[m] & 1, v)) return efail(e, rc, "ensemble_run_steps: member " + std::to_string(m) + ": " + c->err);
+        put(m, nStep[m], t[m], v);
+      }
+      k -= kk;
+    }
+    return 0;
+  };
+  std::vector<int> R, launch_of_round;
   R.reserve((size_t)M);
   for (int round = 0;;) {   // every member that still runs has done `round` steps of this call
     R.clear();
@@ -252,26 +339,13 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
     if (rg_copy_h2d(e->d_span, e->h_span, (size_t)M * sizeof(rgpu_tiled::EnsembleSpan), s)) return finish(efail(e, RGPU_EHIP, std::string("ensemble_run_steps: ") + rg_last_error_string()));
     // Constants by value (member R[0]'s, for everybody) or per member from the table: a scan whose sets differ, or any ensemble under
     // the diagnostic option member_params.  The table holds ALL members, running or not, and is written here once for good
-    const bool use_tab = rgpu::options().member_params != 0 || (e->scan && !e->uniform);
-    if (use_tab && !e->d_tab) {
-      if (rg_malloc((void**)&e->d_tab, (size_t)M * sizeof(rgpu_tiled::MemberConst)) || (!e->h_tab && rg_host_alloc((void**)&e->h_tab, (size_t)M * sizeof(rgpu_tiled::MemberConst)))) {
-        rg_free(e->d_tab); e->d_tab = 0;   // (d_tab != 0 means "filled and copied")
-        return finish(efail(e, RGPU_ENOMEM, "ensemble_run_steps: allocation of the table of member constants failed"));
-      }
-      for (int m = 0; m < M; ++m) {
-        rgpu_ctx* c = e->ctx[(size_t)m];
-        rgpu_tiled::MemberConst& mc = e->h_tab[m];
-        std::memset(&mc, 0, sizeof(mc));
-        mc.g = c->g;
-        mc.g.hdt = 0.0; mc.g.hgx = 0.0; mc.g.hgy = 0.0; mc.g.hgz = 0.0;
-        mc.k = clock_const(c);
-        mc.rc = rot_coef(c, 0.0);
-      }
-      if (rg_copy_h2d(e->d_tab, e->h_tab, (size_t)M * sizeof(rgpu_tiled::MemberConst), s)) {
-        const std::string why = rg_last_error_string();
-        rg_free(e->d_tab); e->d_tab = 0;
-        return finish(efail(e, RGPU_EHIP, "ensemble_run_steps: copy of the table of member constants: " + why));
-      }
+    const bool use_tab = ensemble_uses_table(e);
+    if (const int rt = use_tab ? ensemble_table(e, s, "ensemble_run_steps") : RGPU_OK) return finish(rt);
+    // sampling: every member's step number at the start of the batch, for the kernels' "is this step of member m a multiple of every"
+    if (mon) {
+      if (const int rt = ensemble_monitor_buffers(e, "ensemble_run_steps")) return finish(rt);
+      for (int m = 0; m < M; ++m) { e->h_mspan[m].nStep0 = nStep[m]; e->h_mspan[m].parity = -1; }
+      if (rg_copy_h2d(e->d_mspan, e->h_mspan, (size_t)M * sizeof(rgpu_tiled::MonitorSpan), s)) return finish(efail(e, RGPU_EHIP, std::string("ensemble_run_steps: ") + rg_last_error_string()));
     }
     rgpu_ctx* c0 = e->ctx[(size_t)R[0]];
     DevParams g = c0->g;
@@ -291,7 +365,8 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
     const size_t pool = (size_t)M * e->stride;
     const unsigned stride = (unsigned)e->stride;
     const int nb = left < kBatch ? left : kBatch;
-    int queued = 0, rc = 0;
+    int queued = 0, rc = 0, nlaunch = 0;
+    launch_of_round.assign((size_t)nb, -1);   // the log slot of the monitor launch queued behind round r, -1: none
     for (; queued < nb; ++queued) {
       StepClock* rec = e->d_clk + (size_t)queued * M;
       if (use_tab ? rgpu_tiled::launch_scan_clock(s, M, slots, e->d_tab, e->d_span, queued ? rec - M : 0, rec)
@@ -309,11 +384,25 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
                               : rgpu_tiled::hydro2d_ensemble_step(s, M, g, in, out, stride, slots, images, rec);
       if (rs) { rc = -1; break; }
       for (int m : R) { e->ctx[(size_t)m]->rec.scanned(pout, RG_DT_SLOTS); e->ctx[(size_t)m]->rec.ghosts_written(pout); }
+      if (mon) {
+        // the monitor of the state this round wrote, when some running member's step number after it is a multiple of every; which
+        // members really took the step is in the records: the kernels look there, the host when it walks them below
+        bool any = false;
+        for (int m : R) any = any || (nStep[m] + queued + 1) % mon->every == 0;
+        if (any) {
+          if (rgpu_tiled::launch_ensemble_monitor(s, M, g, use_tab ? e->d_tab : 0, e->U, stride, e->d_mspan, rec, queued + 1, mon->every, pout, e->d_mpart, e->d_mlog, (unsigned)nlaunch)) {
+            rc = -1; ++queued;   // (the round itself is queued and counts; its samples are lost with the error)
+            break;
+          }
+          launch_of_round[(size_t)queued] = nlaunch++;
+        }
+      }
     }
     // a launch that failed after `queued` complete rounds were queued: those still run -- read their records and advance the members
     // for them before reporting (as rgpu_run_steps_log)
     const std::string launch_err = rc ? std::string(rg_last_error_string()) : std::string();
-    if (queued > 0 && (rg_copy_d2h(e->h_clk, e->d_clk, (size_t)queued * M * sizeof(StepClock), s) || rg_stream_sync(s))) {
+    if (queued > 0 && (rg_copy_d2h(e->h_clk, e->d_clk, (size_t)queued * M * sizeof(StepClock), s) ||
+                       (nlaunch > 0 && rg_copy_d2h(e->h_mlog, e->d_mlog, (size_t)nlaunch * M * MON_NQ * sizeof(double), s)) || rg_stream_sync(s))) {
       for (int m : R) e->ctx[(size_t)m]->rec.forget();
       return finish(efail(e, RGPU_EHIP, std::string("ensemble_run_steps: read-back of the records: ") + rg_last_error_string()));
     }
@@ -327,8 +416,11 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
         dt[m] = d;
         t[m] += d;
         if (dt_log) dt_log[(size_t)m * nsteps + done[m] + r] = d;
+        if (mon && launch_of_round[(size_t)r] >= 0 && (n0 + r + 1) % mon->every == 0)   // exactly the slots the kernels filled: this step ran and qualifies
+          put(m, n0 + r + 1, t[m], e->h_mlog + ((size_t)launch_of_round[(size_t)r] * M + m) * MON_NQ);
       }
       nStep[m] += r;
+      c->cur = nStep[m] & 1;
       done[m] += r;
       if (r > advanced) advanced = r;
       if (r < queued) {   // its later steps were no-ops: the state of step n0 + r is the last one written, slots and ghost cells are still its
@@ -347,6 +439,64 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
 #endif
   }
   return finish(RGPU_OK);
+}
+}  // namespace
+
+extern "C" {
+
+int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, int* nStep, double* t, double* dt, double* dt_log, int* done, int* stop, int* fused_steps) {
+  if (!e) return RGPU_EINVAL;
+  if (e->members < 1) return efail(e, RGPU_EINVAL, "ensemble_run_steps: the ensemble was not created");
+  if (!nStep || !t || !dt || !done) return efail(e, RGPU_EINVAL, "ensemble_run_steps: null pointer");
+  return ensemble_run_impl(e, nsteps, tEnd, nStep, t, dt, dt_log, done, stop, fused_steps, 0);
+}
+
+int rgpu_ensemble_run_steps_monitored(rgpu_ensemble* e, int nsteps, const double* tEnd, int* nStep, double* t, double* dt, double* dt_log, int* done, int* stop,
+                                      int* fused_steps, int every, int* mon_n, int* mon_step, double* mon_t, double* mon) {
+  if (!e) return RGPU_EINVAL;
+  if (e->members < 1) return efail(e, RGPU_EINVAL, "ensemble_run_steps_monitored: the ensemble was not created");
+  if (!nStep || !t || !dt || !done || !mon_n || !mon_step || !mon_t || !mon) return efail(e, RGPU_EINVAL, "ensemble_run_steps_monitored: null pointer");
+  if (every < 1) return efail(e, RGPU_EINVAL, "ensemble_run_steps_monitored: every must be >= 1");
+  for (int m = 0; m < e->members; ++m) mon_n[m] = 0;
+  const EnsembleMon em = {every, (nsteps > 0 ? nsteps : 0) / every + 1, mon_n, mon_step, mon_t, mon};
+  return ensemble_run_impl(e, nsteps, tEnd, nStep, t, dt, dt_log, done, stop, fused_steps, &em);
+}
+
+int rgpu_ensemble_monitor(rgpu_ensemble* e, double* out) {
+  if (!e) return RGPU_EINVAL;
+  if (e->members < 1) return efail(e, RGPU_EINVAL, "ensemble_monitor: the ensemble was not created");
+  if (!out) return efail(e, RGPU_EINVAL, "ensemble_monitor: null pointer");
+  rg_set_device(e->device);
+  const int M = e->members;
+#ifdef RGPU_TILED_ENSEMBLE2D
+  // one kernel pair for all members (hip/ensemble_monitor.h, outside a batch: no records, each member's own parity), one read-back
+  const rg_stream_t s = (rg_stream_t)0;
+  if (const int rt = ensemble_monitor_buffers(e, "ensemble_monitor")) return rt;
+  const bool use_tab = ensemble_uses_table(e);
+  if (const int rt = use_tab ? ensemble_table(e, s, "ensemble_monitor") : RGPU_OK) return rt;
+  for (int m = 0; m < M; ++m) { e->h_mspan[m].nStep0 = 0; e->h_mspan[m].parity = e->ctx[(size_t)m]->cur; }
+  if (rg_copy_h2d(e->d_mspan, e->h_mspan, (size_t)M * sizeof(rgpu_tiled::MonitorSpan), s) ||
+      rgpu_tiled::launch_ensemble_monitor(s, M, e->ctx[0]->g, use_tab ? e->d_tab : 0, e->U, (unsigned)e->stride, e->d_mspan, 0, 0, 1, -1, e->d_mpart, e->d_mlog, 0u) ||
+      rg_copy_d2h(e->h_mlog, e->d_mlog, (size_t)M * MON_NQ * sizeof(double), s) || rg_stream_sync(s))
+    return efail(e, RGPU_EHIP, std::string("ensemble_monitor: ") + rg_last_error_string());
+  std::memcpy(out, e->h_mlog, (size_t)M * MON_NQ * sizeof(double));
+#else
+  for (int m = 0; m < M; ++m) {   // no ensemble kernels in this build: member by member through the flat monitor
+    rgpu_ctx* c = e->ctx[(size_t)m];
+    if (const int rc = rgpu_state_monitor(c, c->cur, out + (size_t)m * MON_NQ)) return efail(e, rc, "ensemble_monitor: member " + std::to_string(m) + ": " + c->err);
+  }
+#endif
+  return RGPU_OK;
+}
+
+size_t rgpu_ensemble_monitor_device_bytes(const rgpu_params* p, int members) {
+  std::string why;
+  if (ensemble_validate(p, members, &why)) return 0;
+#ifdef RGPU_TILED_ENSEMBLE2D
+  return (size_t)members * (sizeof(rgpu_tiled::MonitorSpan) + (monitor_part_doubles(*p) + (size_t)rgpu_ctx::kClockBatch * MON_NQ) * sizeof(double));
+#else
+  return 0;
+#endif
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 // [n * members + m]) so that the host reads the records of a batch back in one contiguous copy.
 // ensemble_scan.h (included at the end): the same three kernels with DevParams / RotCoef / ClockConst per member, read from a table in
 // device memory instead of the kernel arguments -- a parameter scan (rgpu_ensemble_create_scan).
+// ensemble_monitor.h (after it): the monitor of kernels_monitor.h with the member as the second grid dimension.
 #pragma once
 #include "tiled_hydro2d.h"
 #include "tiled_mhd2d.h"
@@ -139,3 +140,4 @@ inline int mhd2d_ensemble_step(rg_stream_t s, int members, const DevParams& g, c
 }  // namespace rgpu_tiled
 
 #include "ensemble_scan.h"   // the same kernels with per-member constants from a device table (parameter scans)
+#include "ensemble_monitor.h"   // per-member totals and extrema sampled on the device inside a batch (kernels_monitor.h)

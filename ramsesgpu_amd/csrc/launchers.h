@@ -6,6 +6,7 @@
 #include "kernels_hydro.h"
 #include "kernels_mhd2d.h"
 #include "kernels_mhd3d.h"
+#include "kernels_monitor.h"   // the monitor of a 2D state: per-cell terms, summation order, flat functors
 #include "step_clock_rec.h"   // StepClock: the time step as a device record (kernels with a `clk` member read it instead of their by-value arguments)
 
 namespace rgpu_dev {

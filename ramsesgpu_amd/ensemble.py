@@ -2,12 +2,17 @@
 its own state, dt sequence and end time, advanced by one step-kernel launch and one clock-kernel launch per step for all of them.
 `Ensemble(p, M)`: M boxes of one parameter set; `Ensemble.scan([p_0, ..])`: a parameter scan, one set per member.
 No numerics live here: `Ensemble` owns the C object, `member(m)` is a `Solver` view of one member's borrowed context."""
+import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _capi
 from .solver import RgpuError, Solver, load_library
+
+
+# the series of one member out of run_steps_monitored: step numbers [n], times [n], values [n, 10] (columns _capi.MON_NAMES)
+MonitorSeries = collections.namedtuple("MonitorSeries", "step t values")
 
 
 class _Member(Solver):
@@ -90,11 +95,31 @@ class Ensemble:
         for v, U0 in zip(self._views, U0s):
             v.start(U0, 0)
 
+    def monitor(self):
+        """rgpu_ensemble_monitor: the ten monitor quantities (_capi.MON_NAMES) of every member's current state, ndarray [members, 10]"""
+        out = np.zeros((self.members, _capi.MON_NQ))
+        rc = self.lib.rgpu_ensemble_monitor(self.ens, out.ctypes.data_as(_capi.c_double_p))
+        if rc:
+            raise RgpuError("rgpu_ensemble_monitor failed (%d): %s" % (rc, self.lib.rgpu_ensemble_last_error(self.ens).decode()))
+        return out
+
+    def monitor_device_bytes(self):
+        return int(self.lib.rgpu_ensemble_monitor_device_bytes(C.byref(self.p), self.members))
+
+    def run_steps_monitored(self, nsteps, every, tEnd=None):
+        """rgpu_ensemble_run_steps_monitored: run_steps, and member m sampled on the device after each of its steps that brings its nStep
+        to a multiple of `every`.  Returns (done, stop, fused_steps, samples): samples[m] is a MonitorSeries with .step [n], .t [n]
+        (the member's time after that step) and .values [n, 10] (columns _capi.MON_NAMES)"""
+        return self._run(nsteps, tEnd, int(every))
+
     def run_steps(self, nsteps, tEnd=None):
         """rgpu_ensemble_run_steps: up to nsteps steps of every member (tEnd: None, one end time for all, or one per member).
         Returns (done, stop, fused_steps): per member the steps taken and 0 or why there were fewer (1: tEnd reached, 2 / 3: its time step
         broke down), and the number of step rounds that went through the fused launch.  Every member view keeps its nStep, totalTime,
         dt and the dt_log of this call."""
+        return self._run(nsteps, tEnd, None)[:3]
+
+    def _run(self, nsteps, tEnd, every):
         M, n = self.members, int(nsteps)
         ns = (C.c_int * M)(*[v.nStep for v in self._views])
         ts = (C.c_double * M)(*[v.totalTime for v in self._views])
@@ -104,10 +129,23 @@ class Ensemble:
             ends = (C.c_double * M)(*([float(tEnd)] * M if np.isscalar(tEnd) else [float(x) for x in tEnd]))
         log = (C.c_double * (M * max(n, 1)))()
         done, stop, fused = (C.c_int * M)(), (C.c_int * M)(), C.c_int(0)
-        rc = self.lib.rgpu_ensemble_run_steps(self.ens, n, ends, ns, ts, ds, log, done, stop, C.byref(fused))
+        if every is None:
+            rc = self.lib.rgpu_ensemble_run_steps(self.ens, n, ends, ns, ts, ds, log, done, stop, C.byref(fused))
+            what = "rgpu_ensemble_run_steps"
+        else:
+            cap = max(n, 0) // max(every, 1) + 1
+            mon_n, mon_step = (C.c_int * M)(), np.zeros((M, cap), dtype=np.intc)
+            mon_t, mon = np.zeros((M, cap)), np.zeros((M, cap, _capi.MON_NQ))
+            rc = self.lib.rgpu_ensemble_run_steps_monitored(self.ens, n, ends, ns, ts, ds, log, done, stop, C.byref(fused), every, mon_n,
+                                                            mon_step.ctypes.data_as(C.POINTER(C.c_int)), mon_t.ctypes.data_as(_capi.c_double_p),
+                                                            mon.ctypes.data_as(_capi.c_double_p))
+            what = "rgpu_ensemble_run_steps_monitored"
         for m, v in enumerate(self._views):
             v.nStep, v.totalTime, v.dt = ns[m], ts[m], ds[m]
             v.dt_log = [log[m * n + i] for i in range(done[m])]
         if rc:
-            raise RgpuError("rgpu_ensemble_run_steps failed (%d): %s" % (rc, self.lib.rgpu_ensemble_last_error(self.ens).decode()))
-        return list(done), list(stop), fused.value
+            raise RgpuError("%s failed (%d): %s" % (what, rc, self.lib.rgpu_ensemble_last_error(self.ens).decode()))
+        samples = None
+        if every is not None:
+            samples = [MonitorSeries(mon_step[m, :mon_n[m]].astype(int), mon_t[m, :mon_n[m]].copy(), mon[m, :mon_n[m]].copy()) for m in range(M)]
+        return list(done), list(stop), fused.value, samples

@@ -249,6 +249,14 @@ class Solver:
         self._chk(self.lib.rgpu_state_checksum(self.ctx, parity, C.byref(out)), "state_checksum")
         return int(out.value)
 
+    def state_monitor(self, parity=None):
+        """the ten monitor quantities of U[parity] (default: nStep % 2), columns _capi.MON_NAMES: totals of mass, momenta and energies,
+        min density, min internal energy, max |div B| over the interior of a 2D state, raw (rgpu_state_monitor, include/rgpu.h)"""
+        out = np.zeros(_capi.MON_NQ)
+        par = self.nStep % 2 if parity is None else int(parity)
+        self._chk(self.lib.rgpu_state_monitor(self.ctx, par, out.ctypes.data_as(_capi.c_double_p)), "state_monitor")
+        return out
+
     def history_turbulence(self, nStep=None):
         """history_turbulence (MHDRunBase.cpp:3626-3810) reduced on the device: the 18 columns after totalTime and dt"""
         parity = (self.nStep if nStep is None else nStep) % 2

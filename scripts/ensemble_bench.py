@@ -17,10 +17,17 @@ Parameter scans (rgpu_ensemble_create_scan: one parameter set per member, the me
                     the same M parameter sets as M lone contexts stepped one after another (no new API: with --baseline-lib also on
                     the baseline build, which is the column the acceptance of DESIGN 3.6.1 is phrased against)
 
+Monitors (rgpu_ensemble_run_steps_monitored: per-member totals and extrema sampled on the device inside the batches):
+  --monitor-every K adds (m): the ensemble of (a) run with sampling every K steps, and (d): what gives a user the same series through
+                    the API every build with ensembles has -- rgpu_ensemble_run_steps in pieces of K steps and a download of every
+                    member's state after each piece (the reduction in numpy that would follow is NOT timed); with --baseline-lib (d) and
+                    (a) also on the baseline build.  The windows of (m) and (d) are whole multiples of K steps.
+
 --single-box (with --baseline-lib) adds (c): ONE box stepped with rgpu_run_steps on this build and on the baseline build, taking turns,
 for the 2D step kernels whose bodies the ensemble shares -- Orszag-Tang, Kelvin-Helmholtz and Rayleigh-Taylor (uniform gravity: its
 instantiation of the hydro kernel is the one whose register count moved) at --single-size."""
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -32,7 +39,43 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+from ramsesgpu_amd import _capi  # noqa: E402
 from ramsesgpu_amd.solver import Library, Solver, lib_path  # noqa: E402
+
+class _Absent:
+    """stands in for an entry point a library of an earlier commit does not export: the binding's declarations go through, a call raises"""
+
+    def __init__(self, name):
+        self.name, self.restype, self.argtypes = name, None, None
+
+    def __call__(self, *args):
+        raise RuntimeError("%s is not in this build of the library" % self.name)
+
+
+class _OlderCDLL(ctypes.CDLL):
+    def __getattr__(self, name):
+        try:
+            return super().__getattr__(name)
+        except AttributeError:
+            if not name.startswith("rgpu"):
+                raise
+            f = _Absent(name)
+            setattr(self, name, f)
+            return f
+
+
+def older_library(path):
+    """--baseline-lib: another build of the library, possibly of a commit whose ABI lacks entry points the binding declares"""
+    L = Library.__new__(Library)
+    L.path, L.lib = path, _OlderCDLL(path)
+    _capi.declare_host_api(L.lib)
+    _capi.declare_device_api(L.lib)
+    return L
+
+
+def has(lib, name):
+    return not isinstance(getattr(lib.lib, name), _Absent)
+
 
 WORKLOADS = {"kelvin-helmholtz": "kelvin_helmholtz_gpu_2d", "orszag-tang": "orszag-tang", "rayleigh-taylor": "rayleigh_taylor_gpu_2d"}
 
@@ -91,14 +134,18 @@ class Replicas:
 
 
 class OneEnsemble:
-    """mode (a); member_params: (a'), the library option set around every call; ps a list: (s), a scan ensemble"""
+    """mode (a); member_params: (a'), the library option set around every call; ps a list: (s), a scan ensemble;
+    monitor_every = K: (m), sampled every K steps; download_every = K: (d), pieces of K steps, every member downloaded after each"""
 
-    def __init__(self, lib, ps, U0s, member_params=False):
+    def __init__(self, lib, ps, U0s, member_params=False, monitor_every=0, download_every=0):
         from ramsesgpu_amd.ensemble import Ensemble
         self.lib, self.member_params = lib, member_params
         self.ens = Ensemble.scan(ps, lib) if isinstance(ps, (list, tuple)) else Ensemble(ps, len(U0s), lib)
         self.ens.start(U0s)
         self.fused = 0
+        self.monitor_every, self.download_every, self.samples = monitor_every, download_every, 0
+        self.piece = monitor_every or download_every   # the windows of (m) and (d) are whole multiples of it
+        self.host = np.empty(tuple(self.ens.p.shape)) if download_every else None
 
     def run(self, k):
         if self.member_params:
@@ -107,6 +154,18 @@ class OneEnsemble:
                 done, stop, fused = self.ens.run_steps(k)
             finally:
                 self.lib.set_option("member_params", old)
+        elif self.monitor_every:
+            done, stop, fused, smp = self.ens.run_steps_monitored(k, self.monitor_every)
+            self.samples += sum(len(x.step) for x in smp)
+        elif self.download_every:
+            done, fused, stop = [0] * self.ens.members, 0, None
+            for n in [self.download_every] * (k // self.download_every) + ([k % self.download_every] if k % self.download_every else []):
+                d, stop, f = self.ens.run_steps(n)
+                done, fused = [a + b for a, b in zip(done, d)], fused + f
+                for m in range(self.ens.members):
+                    v = self.ens.member(m)
+                    v._chk(v.lib.rgpu_download(v.ctx, self.host.ctypes.data, v.nStep % 2), "download")
+                    self.samples += 1
         else:
             done, stop, fused = self.ens.run_steps(k)
         if min(done) != k:
@@ -131,7 +190,9 @@ def calibrate(mode, window):
     while True:
         dt = timed(mode, k)
         if dt > 0.2 * window or k >= 1 << 20:
-            return max(8, int(k * 1.15 * window / dt))
+            k = max(8, int(k * 1.15 * window / dt))
+            piece = getattr(mode, "piece", 0)
+            return (k + piece - 1) // piece * piece if piece else k
         k *= 4
 
 
@@ -148,18 +209,19 @@ def main():
     ap.add_argument("--single-size", type=int, default=512)
     ap.add_argument("--member-params", action="store_true", help="(a'): the equal boxes of (a) with option member_params = 1 (the table kernels)")
     ap.add_argument("--scan", default=None, metavar="KEY", help="(s) / (b_s): M boxes with hydro.KEY (gamma0) spread over +-10 %% of the ini value")
+    ap.add_argument("--monitor-every", type=int, default=0, metavar="K", help="(m) / (d): the ensemble sampled every K steps on the device / run in pieces of K steps with a download of every member")
     ap.add_argument("--no-replicas", action="store_true", help="leave out (b), the equal boxes as lone contexts (profiles/ensemble_bench.json has it)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lib = Library(lib_path(a.arith))
-    base_lib = Library(a.baseline_lib) if a.baseline_lib else None
+    base_lib = older_library(a.baseline_lib) if a.baseline_lib else None
     try:
         import ramsesgpu_amd.ensemble  # noqa: F401
         have_ensemble = True
     except ImportError:
         have_ensemble = False
     have_scan = have_ensemble and hasattr(ramsesgpu_amd.ensemble.Ensemble, "scan")
-    base_has_ensemble = bool(base_lib) and hasattr(base_lib.lib, "rgpu_ensemble_create")
+    base_has_ensemble = bool(base_lib) and has(base_lib, "rgpu_ensemble_create")
     rows = []
     for w in a.workloads.split(","):
         for size in (int(s) for s in a.sizes.split(",")):
@@ -178,6 +240,15 @@ def main():
                     modes["a_member_params"] = OneEnsemble(lib, p, U0s, member_params=True)
                     if base_has_ensemble:
                         modes["a_ensemble_baseline"] = OneEnsemble(base_lib, base_lib.params_from_ini(ini(WORKLOADS[w]), ov), U0s)
+                if a.monitor_every and have_ensemble:
+                    K = a.monitor_every
+                    modes["m_monitored"] = OneEnsemble(lib, p, U0s, monitor_every=K)
+                    modes["d_download"] = OneEnsemble(lib, p, U0s, download_every=K)
+                    if base_has_ensemble:
+                        pb = base_lib.params_from_ini(ini(WORKLOADS[w]), ov)
+                        modes["d_download_baseline"] = OneEnsemble(base_lib, pb, U0s, download_every=K)
+                        if "a_ensemble_baseline" not in modes:
+                            modes["a_ensemble_baseline"] = OneEnsemble(base_lib, pb, U0s)
                 if a.scan:
                     sets = scan_sets(lib, WORKLOADS[w], ov, a.scan, M)
                     Us = [member_state(lib, WORKLOADS[w], o, q, m) for m, (o, q) in enumerate(sets)]   # each set's own initial condition
@@ -201,6 +272,8 @@ def main():
                 for name, mode in modes.items():
                     if isinstance(mode, OneEnsemble):
                         row[name]["fused_rounds"] = mode.fused
+                        if mode.piece:
+                            row[name]["every"], row[name]["samples"] = mode.piece, mode.samples
                 if a.scan:
                     row["scan"] = {"key": a.scan, "values": [getattr(q, a.scan) for _, q in sets]}
                 for mode in modes.values():
