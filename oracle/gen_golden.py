@@ -147,6 +147,17 @@ CASES = {
     "mri_8x16x8_visc_res": ("mhd_mri_3d", "mesh.nx=8;mesh.ny=16;mesh.nz=8;MRI.amp=0.2;hydro.nu=1e-6;MHD.eta=2e-6;run.nstepmax=8;run.noutput=1000", [8]),
     "implode3d_12_visc": ("implode3d", "mesh.nx=12;mesh.ny=12;mesh.nz=12;hydro.riemannSolver=hllc;hydro.nu=0.002;run.nstepmax=6;run.noutput=100", [6]),
     "blast2d_24x36_visc": ("blast2d", "mesh.nx=24;mesh.ny=36;hydro.nu=0.001;run.nstepmax=8;run.noutput=100", [8]),
+    # ... on rough states with coefficients that matter: the diffusion number max(nu, eta) dt / min(dx, dy, dz)^2 stays within
+    # 0.02 .. 0.2 on every step (tests/test_oracle_golden.py asserts it).  Random velocity fields and discontinuities, dx != dy != dz in
+    # 3D hydro and 3D MHD, open z faces, the 2D rotating call site, isothermal 2D.
+    "turb_mhd_10x12x14_visc_res": ("turbulence_mhd", "mesh.nx=10;mesh.ny=12;mesh.nz=14;turbulence.edot=0.0;hydro.nu=0.1;MHD.eta=0.2;output.outputVtk=yes;output.outputHdf5=no;output.ghostIncluded=no;run.nstepmax=8;run.noutput=1000", [8]),
+    "turb_hydro_10x12x14_visc": ("turbulence_hydro", "mesh.nx=10;mesh.ny=12;mesh.nz=14;turbulence.edot=0.0;hydro.nu=0.06;output.outputVtk=yes;output.outputHdf5=no;output.ghostIncluded=no;run.nstepmax=8;run.noutput=1000", [8]),
+    "mri_8x12x10_amp_visc_res": ("mhd_mri_3d", "mesh.nx=8;mesh.ny=12;mesh.nz=10;MRI.amp=0.5;hydro.nu=1.5e-5;MHD.eta=3e-5;run.nstepmax=10;run.noutput=1000", [10]),
+    "briowu_z_8x6x16_visc_res_open": ("mhd_BrioWu", "mesh.nx=8;mesh.ny=6;mesh.nz=16;BrioWu.direction=2;MHD.implementationVersion=4;MHD.eta=0.1;hydro.nu=0.05;mesh.boundary_zmin=2;mesh.boundary_zmax=2;run.nstepmax=8;run.noutput=1000", [8]),
+    "implode3d_10x8x6_rand_visc": ("implode3d", "mesh.nx=10;mesh.ny=8;mesh.nz=6;implode.amplitude=0.3;implode.seed=7;hydro.riemannSolver=hllc;hydro.nu=0.03;run.nstepmax=8;run.noutput=1000", [8]),
+    "kh2d_rand_20x28_visc": ("kelvin_helmholtz_cpu_2d", "mesh.nx=20;mesh.ny=28;hydro.nu=0.01;run.nstepmax=12;run.noutput=1000", [12]),
+    "ot2d_20x28_iso_visc_res": ("orszag-tang", "mesh.nx=20;mesh.ny=28;hydro.cIso=0.9;hydro.nu=0.01;MHD.eta=0.02;run.nstepmax=12;run.noutput=1000", [12]),
+    "ot2d_16x24_rot_visc_res": ("orszag-tang", "mesh.nx=16;mesh.ny=24;MHD.omega0=0.4;hydro.nu=0.01;MHD.eta=0.02;run.nstepmax=12;run.noutput=1000", [12]),
     "sod2d_32x8": ("hydro_sod2d", "mesh.nx=32;mesh.ny=8;run.nstepmax=10;run.noutput=100", [0, 10]),
 }
 

@@ -213,6 +213,16 @@ int orc_godunov_unsplit(const rgpu_params* p, double* Uold, double* Unew, double
   return 0;
 }
 
+// the dissipative stage alone ([hydro] nu / [MHD] eta > 0; no-op otherwise) on a state whose Godunov update is done: its own ghost
+// fill (make_all_boundaries(U, totalTime, dt)), resistive emf + CT + energy flux, viscous fluxes, as the steps call it
+int orc_dissipative_stage(const rgpu_params* p, double* U, double dt, double totalTime) {
+  const int rc = check_scope(p);
+  if (rc) return rc;
+  Ctx c(*p);
+  dissipative_stage(c, U, dt, totalTime);
+  return 0;
+}
+
 // godunov_unsplit of a z window of a larger 3D box.  A cell's new value depends only on the planes within ghostWidth of it, so
 // the step of the whole box can be checked window by window.  p describes the window: nz = its w planes, zMin / zMax moved to
 // them, nz_global left at the box's value (a window of one plane is still a 3D step).  Uold holds the window's planes with

@@ -80,6 +80,16 @@ class Oracle:
         assert rc == 0, rc
         return Unew
 
+    def dissipative_stage(self, p, U, dt, totalTime=0.0):
+        """orc_dissipative_stage: the operator-split viscous / resistive stage alone, in place on U (it refills U's ghosts itself, as
+        the steps' call sites do); returns U"""
+        f = self.lib.orc_dissipative_stage
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(RgpuParams), C.c_void_p, C.c_double, C.c_double]
+        rc = f(C.byref(p), self._arr(U), dt, totalTime)
+        assert rc == 0, rc
+        return U
+
     def godunov_unsplit_zwindow(self, p, Uold, dt, totalTime=0.0, nthreads=1):
         """orc_godunov_unsplit_zwindow: one step of a z window (parity_checks.zwindow), its z ghost planes kept as given; returns Unew,
         whose interior planes with their x / y ghost columns are those of the whole box's step.  nthreads > 1: the threaded 3D MHD

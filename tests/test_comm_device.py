@@ -87,6 +87,10 @@ SMALL = [
     ("orszag-tang3d", "mesh.nx=16;mesh.ny=16;mesh.nz=48", 4, 3, 2),
     ("orszag-tang3d", "mesh.nx=16;mesh.ny=16;mesh.nz=32" + OPEN_BC, 4, 2, 1),
     ("orszag-tang3d", "mesh.nx=16;mesh.ny=16;mesh.nz=48" + OPEN_BC, 3, 3, 2),
+    # dissipative stage: the driver's serial path with its second exchange inside the step (appended: RUN_STEPS and CONTRACTED index by position)
+    ("orszag-tang3d", "mesh.nx=16;mesh.ny=16;mesh.nz=32;hydro.nu=0.005;MHD.eta=0.01", 3, 2, 1),
+    ("orszag-tang3d", "mesh.nx=16;mesh.ny=16;mesh.nz=48;hydro.nu=0.005;MHD.eta=0.01", 3, 3, 1),
+    ("mhd_mri_3d", "mesh.nx=16;mesh.ny=24;mesh.nz=40;MRI.amp=0.2;hydro.nu=1.5e-5;MHD.eta=3e-5", 3, 2, 1),   # ... after the shear remap
 ]
 SCHED = ("serial", "overlap", "boundary-first")
 ENV = {"HSA_ENABLE_IPC_MODE_LEGACY": "0", "COMM_DEVICE": "cuda-staged:0"}

@@ -124,6 +124,8 @@ UNCOVERED = [
     ("mhd_BrioWu", "mesh.nx=128;mesh.ny=8"),               # 2D MHD with Neumann faces: no ghost images, the plain loop
     ("rayleigh_taylor_gpu_2d", "mesh.nx=40;mesh.ny=120"),  # gravity: (0.5 dt) g is a kernel argument
     ("jet2d_cpu", "mesh.nx=40;mesh.ny=120"),               # jet inflow: a ghost fill every step
+    ("kelvin_helmholtz_gpu_2d", "mesh.nx=50;mesh.ny=37;hydro.nu=0.01"),   # viscous / resistive stage behind the step: no device clock
+    ("orszag-tang", "mesh.nx=53;mesh.ny=45;MHD.eta=0.02"),                # (csrc/api/entry_clock.h)
 ]
 
 

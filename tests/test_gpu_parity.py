@@ -260,10 +260,15 @@ def test_launch_specialised_kernels_equal_generic_ones(base, ov, gpu_lib):
 
 OPTION_CASES = [("orszag-tang", "mesh.nx=40;mesh.ny=24"), ("kelvin_helmholtz_gpu_2d", "mesh.nx=40;mesh.ny=24"), ("implode3d", "mesh.nx=24;mesh.ny=20;mesh.nz=16;hydro.riemannSolver=hllc"),
                 ("mhd_mri_3d", ""), ("orszag-tang3d", "mesh.nx=24;mesh.ny=20;mesh.nz=16")]
+# ... with the viscous / resistive stage behind the step: no fused CFL scan, the 2D kernels' ghost images stale after it (a list of
+# its own, so that the ids of the cases above stay what they are)
+OPTION_CASES_DISSIPATIVE = [("orszag-tang", "mesh.nx=40;mesh.ny=24;MHD.eta=0.02"), ("kelvin_helmholtz_gpu_2d", "mesh.nx=40;mesh.ny=24;hydro.nu=0.01"),
+                            ("orszag-tang3d", "mesh.nx=24;mesh.ny=20;mesh.nz=16;hydro.nu=0.01;MHD.eta=0.02")]
 
 
 @pytest.mark.parametrize("option,value", [("ghost_images", 0), ("step_clock", 0), ("zseg", 5), ("spec", 0)])
-@pytest.mark.parametrize("base,ov", OPTION_CASES, ids=[c[0] for c in OPTION_CASES])
+@pytest.mark.parametrize("base,ov", OPTION_CASES + OPTION_CASES_DISSIPATIVE,
+                         ids=[c[0] for c in OPTION_CASES] + [c[0] + "-dissipative" for c in OPTION_CASES_DISSIPATIVE])
 def test_diagnostic_options_keep_the_bits(base, ov, option, value, gpu_lib):
     """every diagnostic option of the library (include/rgpu.h, "Environment and options") switches a fast path off or pins a launch
     plan: a batch of steps through rgpu_run_steps gives the same state and the same time steps either way"""
@@ -492,9 +497,16 @@ RUN_STEPS_CASES = [
     ("rayleigh_taylor_gpu_3d_mhd", "mesh.nx=8;mesh.ny=8;mesh.nz=32", 6, False),              # gravity: plain loop
     ("orszag-tang3d", "mesh.nx=12;mesh.ny=12;mesh.nz=16;hydro.nu=0.005;MHD.eta=0.01", 6, False),   # dissipative stage: plain loop
 ]
+# the 2D boxes of the first two lines with the dissipative stage: the plain loop, every step_pre refills the ghosts the stage left stale
+# (a list of its own, so that the ids of the cases above stay what they are)
+RUN_STEPS_DISSIPATIVE = [
+    ("kelvin_helmholtz_gpu_2d", "mesh.nx=96;mesh.ny=64;hydro.nu=0.01", 12, False),
+    ("orszag-tang", "mesh.nx=96;mesh.ny=80;MHD.eta=0.02", 12, False),
+]
 
 
-@pytest.mark.parametrize("base,ov,nsteps,clocked", RUN_STEPS_CASES, ids=[c[0] for c in RUN_STEPS_CASES])
+@pytest.mark.parametrize("base,ov,nsteps,clocked", RUN_STEPS_CASES + RUN_STEPS_DISSIPATIVE,
+                         ids=[c[0] for c in RUN_STEPS_CASES] + [c[0] + "-dissipative" for c in RUN_STEPS_DISSIPATIVE])
 def test_run_steps_equals_the_reference_loop(base, ov, nsteps, clocked, gpu_lib, oracle):
     """rgpu_run_steps(K) == K x oneStepIntegration == the oracle: every double of the state, nStep, t and the last dt -- where the
     time step stays on the device between the fused 2D kernels (csrc/hip/step_clock.h) and where the call falls back to the plain

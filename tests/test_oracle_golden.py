@@ -33,6 +33,27 @@ def test_oracle_reproduces_reference_bit_for_bit(name, case, oracle, product_lib
             assert abs(t - float(g["total_time"])) <= 1e-11 * max(1.0, abs(t))
 
 
+ROUGH_DISSIPATIVE = ["turb_mhd_10x12x14_visc_res", "turb_hydro_10x12x14_visc", "mri_8x12x10_amp_visc_res", "briowu_z_8x6x16_visc_res_open",
+                     "implode3d_10x8x6_rand_visc", "kh2d_rand_20x28_visc", "ot2d_20x28_iso_visc_res", "ot2d_16x24_rot_visc_res"]
+
+
+@pytest.mark.parametrize("name", ROUGH_DISSIPATIVE)
+def test_rough_dissipative_fixtures_carry_a_stage_that_matters(name, product_lib):
+    """the fixtures that pin the viscous / resistive stage on rough states: the explicit diffusion number
+    max(nu, eta) dt / min(dx, dy, dz)^2 of every step of the reference's dt log lies in [0.02, 0.2] -- at 0.02 the stage moves the state
+    by percents, up to 0.2 it amplifies no round-off -- and the reference's output is finite"""
+    case = golden_cases()[name]
+    p = product_lib.params_from_ini(ini(case["base"]), case["overrides"])
+    g = load_golden(name)
+    nsteps = max(case["steps"])
+    dts = g["log_dt"]      # the initial compute_dt, then the dt of every step
+    assert len(dts) >= nsteps and np.isfinite(g["step_%d" % nsteps]).all()
+    h = min(p.dx, p.dy, p.dz) if p.three_d else min(p.dx, p.dy)
+    D = max(p.nu, p.eta if p.mhdEnabled else 0.0) * dts / (h * h)
+    print("%s: diffusion number %.3f .. %.3f" % (name, D.min(), D.max()))
+    assert 0.02 <= D.min() and D.max() <= 0.2, (name, D.min(), D.max())
+
+
 @pytest.mark.parametrize("name", ["mri_8x16x8_history", "ot3d_12_history"])
 def test_oracle_history_matches_reference_history_file(name, oracle, product_lib):
     """the reference writes <prefix>_history.txt with 6 significant digits (MHDRunBase.cpp:3596-3602, 3401-3402): one
