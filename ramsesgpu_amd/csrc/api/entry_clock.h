@@ -53,13 +53,14 @@ int rgpu_clock_open(rgpu_ctx* c, double t0, double tEnd) {
   // every workgroup pays the fold (1024 slot reads, a barrier, the record) -- Orszag-Tang 512^2 (2145 workgroups of the MHD kernel)
   // 0.0439 -> 0.0458, 4096^2 +15 % -- and in the 3D MHD sweep (tried on the rotating path) the extra kernel argument alone moved the
   // register allocation of the z march: 25.1 -> 25.6 ms at 512^3.  Everything else keeps the one-workgroup clock kernel.
-  {
-    const int nwg = ((c->g.isize - 1 + 13) / 14) * ((c->g.jsize - 1 + 13) / 14);   // 16 x 16 thread tiles, 14 x 14 owned cells (tiled_hydro2d.h)
-    // only for the library's own loop (rgpu_run_steps_log: the ghost cells of the input are known to be valid, no piece is queued
-    // between the tick and the step kernel): with the record written by the step kernel, a piece queued in between by an external
-    // driver would read the record of an earlier batch
-    c->fold_mode = c->fold_request && !RG_SYNC_LAUNCH && rgpu_tiled::step_clock_fold_enabled() && !c->g.three_d && !c->p.mhdEnabled && nwg <= 2 * 768;
-  }
+  c->fold_mode = false;
+#if !RG_SYNC_LAUNCH   // (the host emulation has no fused step kernel to fold the clock into)
+  // only for the library's own loop (rgpu_run_steps_log: the ghost cells of the input are known to be valid, no piece is queued
+  // between the tick and the step kernel): with the record written by the step kernel, a piece queued in between by an external
+  // driver would read the record of an earlier batch.  hydro2d_tiles: the workgroups of the fused step (tiled_hydro2d.h)
+  int nbx;
+  c->fold_mode = c->fold_request && rgpu_tiled::step_clock_fold_enabled() && !c->g.three_d && !c->p.mhdEnabled && rgpu_tiled::hydro2d_tiles(c->g, &nbx) <= 2 * 768;
+#endif
   c->fold_pending = false;
   if (c->fold_mode) {   // the two slot arrays the first steps accumulate into / zero: clean (the host loop uses one array at a time)
     c->fold_phase0 = (int)((c->d_red - c->d_red_base) / RG_DT_SLOTS);

@@ -188,15 +188,10 @@ int hydro_core(rgpu_ctx* c, const double* in, double* out, double dt_arg, int a,
   { Phase ph(c, RGPU_T_PRIM); K_hydro_prim<NV> k = {g, in, c->Q}; if (launch_planes<kBlock, 1>(c->stream, g, clip(a - 2, b + 2, ks), k)) return -1; }
   const bool gf = g.grav_on == 2;   // per-cell gravity field: separate instantiations (see half_dt_gravity)
   int rc = 1;   // 1 = not handled by a specialisation
-  if (rgpu::options().spec && g.grav_on == 0) {
-    const int SL1 = SPEC_SLOPE1 | SPEC_NO_GRAVITY, SL2 = SPEC_SLOPE2 | SPEC_NO_GRAVITY;
-    if (spec_matches(SPEC_HYDRO_APPROX | SL1, g)) rc = hydro_flux_trace_spec<ND, NV, SPEC_HYDRO_APPROX | SL1>(c, dtdx, dtdy, dtdz, a, b);
-    else if (spec_matches(SPEC_HYDRO_APPROX | SL2, g)) rc = hydro_flux_trace_spec<ND, NV, SPEC_HYDRO_APPROX | SL2>(c, dtdx, dtdy, dtdz, a, b);
-    else if (spec_matches(SPEC_HYDRO_HLLC | SL1, g)) rc = hydro_flux_trace_spec<ND, NV, SPEC_HYDRO_HLLC | SL1>(c, dtdx, dtdy, dtdz, a, b);
-    else if (spec_matches(SPEC_HYDRO_HLLC | SL2, g)) rc = hydro_flux_trace_spec<ND, NV, SPEC_HYDRO_HLLC | SL2>(c, dtdx, dtdy, dtdz, a, b);
-    else if (spec_matches(SPEC_HYDRO_HLL | SL1, g)) rc = hydro_flux_trace_spec<ND, NV, SPEC_HYDRO_HLL | SL1>(c, dtdx, dtdy, dtdz, a, b);
-    else if (spec_matches(SPEC_HYDRO_HLL | SL2, g)) rc = hydro_flux_trace_spec<ND, NV, SPEC_HYDRO_HLL | SL2>(c, dtdx, dtdy, dtdz, a, b);
-  }
+  // launchers.h: the six no-gravity entries (mutually exclusive, so their order is free; grav_on != 0 picks none).  The dispatcher's
+  // generic tail also instantiates hydro_flux_trace_spec<.., SPEC_NONE>: never called (sp != 0), no new kernel (the functors below)
+  if (const int sp = hydro_pick_spec<false>(g))
+    rc = hydro_spec_dispatch<false>(sp, [&](auto tag) { return hydro_flux_trace_spec<ND, NV, decltype(tag)::value>(c, dtdx, dtdy, dtdz, a, b); });
   if (rc < 0) return -1;
   if (rc == 1) {
     { Phase ph(c, RGPU_T_TRACE); K_hydro_trace<ND, NV> k = {g, c->Q, c->T, dtdx, dtdy, dtdz}; if (launch_planes<kBlock, 1>(c->stream, g, clip(a - 1, b + 1, ks), k)) return -1; }

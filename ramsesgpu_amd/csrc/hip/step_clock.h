@@ -16,11 +16,12 @@
 
 namespace rgpu_tiled {
 
-// One workgroup: folds the RG_DT_SLOTS CFL maxima (and re-zeroes them: the step kernels that follow accumulate the maxima of the
-// state they write), then thread 0 forms the record of the step (step_clock_rec.h: the host's expressions in the host's order).
-// prev: the previous record of the batch (0: the batch starts at t0).
-__global__ void __launch_bounds__(1024) step_clock_kernel(unsigned long long* __restrict__ slots, ClockConst k, double t0, double tEnd,
-                                                        const StepClock* prev, StepClock* out) {
+// The tick of one box, by one workgroup of 1024 threads -- the one body of step_clock_kernel, ensemble_clock_kernel and
+// scan_clock_kernel (ensemble2d.h, ensemble_scan.h: one workgroup per member), which differ only in where these arguments come from.
+// Folds the RG_DT_SLOTS CFL maxima at `slots`, then thread 0 forms the record of the step (step_clock_rec.h: the host's expressions
+// in the host's order) from *kp, read there and nowhere else.  prev: the previous record of the batch (0: the batch starts at t0).
+__device__ __forceinline__ void clock_tick_body(unsigned long long* __restrict__ slots, const ClockConst* kp, const StepClock* prev, const double& t0,
+                                                const double& tEnd, StepClock* out) {
   __shared__ double red[16];
   __shared__ int runs;
   const int t = (int)threadIdx.x;
@@ -34,6 +35,7 @@ __global__ void __launch_bounds__(1024) step_clock_kernel(unsigned long long* __
     double m = red[0];
 #pragma unroll
     for (int w = 1; w < 16; ++w) m = fmax(m, red[w]);
+    const ClockConst k = *kp;
     StepClock r;
     step_clock_form(k, m, prev ? prev->t_next : t0, tEnd, prev ? prev->stop : 0, &r);
     *out = r;
@@ -43,6 +45,11 @@ __global__ void __launch_bounds__(1024) step_clock_kernel(unsigned long long* __
   // a step that runs accumulates the maxima of the state it writes into zeroed slots; a stopped one (and every step behind it) is a
   // no-op and leaves the slots as they are: after the batch they still hold the maxima of the last state written
   if (runs) slots[t] = 0ull;
+}
+
+__global__ void __launch_bounds__(1024) step_clock_kernel(unsigned long long* __restrict__ slots, ClockConst k, double t0, double tEnd,
+                                                        const StepClock* prev, StepClock* out) {
+  clock_tick_body(slots, &k, prev, t0, tEnd, out);
 }
 
 // the fold of csrc/step_clock_rec.h (ClockFold) for a workgroup of NT threads; red: NT / 64 doubles of LDS of its own.  Contains one

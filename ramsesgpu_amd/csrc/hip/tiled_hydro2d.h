@@ -195,36 +195,31 @@ __global__ void __launch_bounds__(TX * TY) hydro2d_step_kernel(DevParams g, int 
   hydro2d_step_body<TX, TY, SPEC>(g, nbx, Uin, Uout, dtdx, dtdy, dt_slots, images);
 }
 
-template <int TX, int TY, int SPEC>
-inline int launch_hydro2d_step(rg_stream_t s, const DevParams& g, const double* in, double* out, double dtdx, double dtdy, unsigned long long* dt_slots, int images, const StepClock* clk, const ClockFold& fold) {
-  const int nbx = (g.isize - 1 + (TX - 2) - 1) / (TX - 2);   // owners cover i in [1, nbx*(TX-2)] plus column 0
-  const int nby = (g.jsize - 1 + (TY - 2) - 1) / (TY - 2);
-  hipLaunchKernelGGL((hydro2d_step_kernel<TX, TY, SPEC>), dim3((unsigned)(nbx * nby)), dim3(TX * TY), 0, s, g, nbx, in, out, dtdx, dtdy, dt_slots, images, clk, fold);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+// The tile and the grid of a fused 2D hydro launch, single box or ensemble: H2_TX x H2_TY threads finish (H2_TX-2) x (H2_TY-2) cells,
+// owners cover i in [1, nbx*(H2_TX-2)] plus column 0.  Returns the tiles of a box (the workgroups of the single-box step), *nbx: those along x.
+constexpr int H2_TX = 16, H2_TY = 16;
+inline int hydro2d_tiles(const DevParams& g, int* nbx) {
+  *nbx = (g.isize - 1 + (H2_TX - 2) - 1) / (H2_TX - 2);
+  return *nbx * ((g.jsize - 1 + (H2_TY - 2) - 1) / (H2_TY - 2));
 }
 
 // configurations the fused 2D hydro step covers (the per-cell gravity field runs the flat kernels' own instantiations)
 inline bool hydro2d_step_covers(const DevParams& g) { return tiled_enabled() && !g.three_d && !g.mhd && g.nvar == 4 && g.grav_on != 2; }
 
 // The whole 2D hydro step U -> Unew.  dt_slots: RG_DT_SLOTS device slots for the CFL maximum of the new state (reset by the caller),
-// or 0; images: see the kernel.  Returns 0 = done, 1 = not covered (the caller runs the flat kernels), < 0 = launch error.
+// or 0; images: see the kernel.  The instantiation: launchers.h (hydro_pick_spec, the list with the uniform-gravity entries).
+// Returns 0 = done, 1 = not covered (the caller runs the flat kernels), < 0 = launch error.
 inline int hydro2d_step(rg_stream_t s, const DevParams& g, const double* in, double* out, double dtdx, double dtdy, unsigned long long* dt_slots, int images, const StepClock* clk = 0,
                         const ClockFold* fold_in = 0) {
   if (!hydro2d_step_covers(g)) return 1;
   ClockFold fold;
   if (fold_in) fold = *fold_in; else { fold.prev = 0; fold.out = 0; fold.in = 0; fold.zero = 0; fold.t0 = 0.0; fold.tEnd = 0.0; }
-  const bool no_spec = !rgpu::options().spec;
-  constexpr int TX = 16, TY = 16;
-#define RG_TRY(SP) if (spec_matches(SP, g)) return launch_hydro2d_step<TX, TY, SP>(s, g, in, out, dtdx, dtdy, dt_slots, images, clk, fold);
-  if (!no_spec) {
-    const int SL1 = SPEC_SLOPE1 | SPEC_NO_GRAVITY, SL2 = SPEC_SLOPE2 | SPEC_NO_GRAVITY;
-    RG_TRY(SPEC_HYDRO_HLLC | SL2) RG_TRY(SPEC_HYDRO_HLLC | SL1)
-    RG_TRY(SPEC_HYDRO_APPROX | SL2) RG_TRY(SPEC_HYDRO_APPROX | SL1)
-    RG_TRY(SPEC_HYDRO_HLL | SL2) RG_TRY(SPEC_HYDRO_HLL | SL1)
-    RG_TRY(SPEC_HYDRO_APPROX | SPEC_SLOPE2) RG_TRY(SPEC_HYDRO_APPROX | SPEC_SLOPE1)   // with uniform gravity
-  }
-#undef RG_TRY
-  return launch_hydro2d_step<TX, TY, SPEC_NONE>(s, g, in, out, dtdx, dtdy, dt_slots, images, clk, fold);
+  int nbx;
+  const dim3 grid((unsigned)hydro2d_tiles(g, &nbx));
+  return hydro_spec_dispatch<true>(hydro_pick_spec<true>(g), [&](auto tag) {
+    hipLaunchKernelGGL((hydro2d_step_kernel<H2_TX, H2_TY, decltype(tag)::value>), grid, dim3(H2_TX * H2_TY), 0, s, g, nbx, in, out, dtdx, dtdy, dt_slots, images, clk, fold);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  });
 }
 
 }  // namespace rgpu_tiled

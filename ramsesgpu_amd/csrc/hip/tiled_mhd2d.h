@@ -208,19 +208,25 @@ __global__ void __launch_bounds__(M2_THREADS, 2) mhd2d_step_kernel(DevParams g, 
 // rewritten by the next ghost fill before anything reads it).  Returns 0 = done, 1 = not covered, < 0 = launch error.
 inline bool mhd2d_step_covers(const DevParams& g) { return tiled_enabled() && !g.three_d && g.mhd && g.grav_on != 2; }
 
+// The grid of a fused 2D MHD launch, single box or ensemble: the tiles of a box over the cells gw .. isize-gw (the CT layer included); *nbx: those along x
+inline int mhd2d_tiles(const DevParams& g, int* nbx) {
+  *nbx = (g.isize - 2 * g.gw + 1 + M2_OX - 1) / M2_OX;
+  return *nbx * ((g.jsize - 2 * g.gw + 1 + M2_OY - 1) / M2_OY);
+}
+
 template <int SPEC_PLAIN>
 // images != 0 (caller: all four faces periodic, nx, ny >= ghost width, nothing modifies the new state after this kernel): the
 // interior cells also write their periodic images, i.e. the output's ghost cells are valid on return
 inline int mhd2d_step(rg_stream_t s, const DevParams& g, const RotCoef& rc, bool spec_plain, const double* U, double* Unew, double dt,
                       unsigned long long* dt_slots, int images, const StepClock* clk = 0) {
   if (!mhd2d_step_covers(g)) return 1;
-  const int nbx = (g.isize - 2 * g.gw + 1 + M2_OX - 1) / M2_OX;   // cells gw .. isize-gw (the CT layer included)
-  const int nby = (g.jsize - 2 * g.gw + 1 + M2_OY - 1) / M2_OY;
+  int nbx;
+  const dim3 grid((unsigned)mhd2d_tiles(g, &nbx));
   const double dtdx = dt / g.dx, dtdy = dt / g.dy;
   if (spec_plain)
-    hipLaunchKernelGGL((mhd2d_step_kernel<SPEC_PLAIN>), dim3((unsigned)(nbx * nby)), dim3(M2_THREADS), 0, s, g, rc, nbx, U, Unew, dt, dtdx, dtdy, dt_slots, images, clk);
+    hipLaunchKernelGGL((mhd2d_step_kernel<SPEC_PLAIN>), grid, dim3(M2_THREADS), 0, s, g, rc, nbx, U, Unew, dt, dtdx, dtdy, dt_slots, images, clk);
   else
-    hipLaunchKernelGGL((mhd2d_step_kernel<SPEC_NONE>), dim3((unsigned)(nbx * nby)), dim3(M2_THREADS), 0, s, g, rc, nbx, U, Unew, dt, dtdx, dtdy, dt_slots, images, clk);
+    hipLaunchKernelGGL((mhd2d_step_kernel<SPEC_NONE>), grid, dim3(M2_THREADS), 0, s, g, rc, nbx, U, Unew, dt, dtdx, dtdy, dt_slots, images, clk);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -7,6 +7,7 @@
 #include "kernels_mhd2d.h"
 #include "kernels_mhd3d.h"
 #include "kernels_monitor.h"   // the monitor of a 2D state: per-cell terms, summation order, flat functors
+#include "rg_options.h"        // option spec (hydro_pick_spec)
 #include "step_clock_rec.h"   // StepClock: the time step as a device record (kernels with a `clk` member read it instead of their by-value arguments)
 
 namespace rgpu_dev {
@@ -54,6 +55,33 @@ inline bool spec_matches(int spec, const DevParams& g) {
   if ((spec & SPEC_HYDRO_HLLC) && g.riemannSolver != 2) return false;
   if ((spec & SPEC_SLOPE1) && !(g.slope_type == 1.0)) return false;
   return true;
+}
+
+// The instantiation list of the hydro kernels specialised on solver and slope type, written once: six solver / slope pairs without
+// gravity, with GRAVITY the two uniform-gravity ones of the single-box 2D step behind them, then the generic one, which assumes
+// nothing.  Calls f(SpecTag<SP>()) for the first entry that `match` accepts: SP is a compile-time constant there.
+template <int SP> struct SpecTag { static constexpr int value = SP; };
+template <bool GRAVITY, class Match, class F>
+inline int hydro_spec_select(Match&& match, F&& f) {
+  constexpr int SL1 = SPEC_SLOPE1 | SPEC_NO_GRAVITY, SL2 = SPEC_SLOPE2 | SPEC_NO_GRAVITY;
+#define RG_TRY(SP) if (match(SP)) return f(SpecTag<(SP)>());
+  RG_TRY(SPEC_HYDRO_HLLC | SL2) RG_TRY(SPEC_HYDRO_HLLC | SL1)
+  RG_TRY(SPEC_HYDRO_APPROX | SL2) RG_TRY(SPEC_HYDRO_APPROX | SL1)
+  RG_TRY(SPEC_HYDRO_HLL | SL2) RG_TRY(SPEC_HYDRO_HLL | SL1)
+  if constexpr (GRAVITY) { RG_TRY(SPEC_HYDRO_APPROX | SPEC_SLOPE2) RG_TRY(SPEC_HYDRO_APPROX | SPEC_SLOPE1) }
+#undef RG_TRY
+  return f(SpecTag<SPEC_NONE>());
+}
+// the entry of the list for these parameters (option spec = 0: the generic one) ...
+template <bool GRAVITY>
+inline int hydro_pick_spec(const DevParams& g) {
+  if (!rgpu::options().spec) return SPEC_NONE;
+  return hydro_spec_select<GRAVITY>([&](int sp) { return spec_matches(sp, g); }, [](auto tag) { return (int)decltype(tag)::value; });
+}
+// ... and f(SpecTag<spec>()) for an entry picked before (anything that is not on the list: the generic one)
+template <bool GRAVITY, class F>
+inline int hydro_spec_dispatch(int spec, F&& f) {
+  return hydro_spec_select<GRAVITY>([&](int sp) { return sp == spec; }, f);
 }
 
 
