@@ -261,8 +261,8 @@ enum { RGPU_CORE_FLUXES = 1, RGPU_CORE_UPDATE = 2, RGPU_CORE_SCAN = 4 };
  * compute_dt): FLUXES | SCAN resets the context's RGPU_DT_SLOTS device slots, every UPDATE | SCAN accumulates the maxima of the
  * cells it updates, rgpu_inv_dt_fused_commit(ctx, parity of the new state) closes the accumulation and returns the number of
  * slots to all-reduce (rgpu_inv_dt_device_slot) before rgpu_inv_dt_result.  rgpu_inv_dt_fused_active tells right after the
- * FLUXES call whether the step can carry the scan; if not (dissipative stage, forcing, open faces on the rotating path, flat
- * kernels) scan with rgpu_inv_dt_accumulate as before. */
+ * FLUXES call whether the step can carry the scan; if not (dissipative stage, forcing, the rotating path with other x faces than the
+ * shearing box's or with open y / z faces, flat kernels) scan with rgpu_inv_dt_accumulate as before. */
 /* 1 when THIS context's configuration lets its update pieces carry the scan (depends on its boundary types: the end slabs of
  * a run may differ from the inner ones).  All ranks must pass the same flag combination and all-reduce the same number of
  * slots: the slab driver takes the minimum over the ranks once and drops RGPU_CORE_SCAN everywhere if any rank says 0. */
@@ -339,7 +339,8 @@ int rgpu_one_step_integration(rgpu_ctx* c, int* nStep, double* t, double* dt);
  * gravity, no rotating frame) the time step itself stays on the device (csrc/hip/step_clock.h: dt = cfl / max 1/dt, the
  * loop condition and t += dt evaluated by a one-workgroup kernel between two steps) and a batch of steps is queued without a host round
  * trip -- at the shipped 2D sizes that round trip costs as much as a third of the step.  Since round 5 the 3D steps do the same (hydro,
- * plain / rotating / shearing-box MHD through the z-marching sweeps: rgpu_clock_capable).  Every other configuration runs the plain loop. */
+ * plain / shearing-box MHD through the z-marching sweeps: rgpu_clock_capable; a rotating box with periodic x faces leaves no CFL maxima
+ * behind -- the reference scans its refilled ghosts -- and runs the plain loop).  Every other configuration runs the plain loop. */
 int rgpu_run_steps(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt);
 /* ... the same, and dt_log[n] = the time step of the n-th step done (the "dt=" column of the reference's log, MHDRunGodunov.cpp:3958);
  * dt_log holds nsteps doubles or is NULL.  If a launch fails after some steps of a batch were queued, *nStep, *t, *dt (and dt_log)

@@ -158,6 +158,16 @@ CASES = {
     "kh2d_rand_20x28_visc": ("kelvin_helmholtz_cpu_2d", "mesh.nx=20;mesh.ny=28;hydro.nu=0.01;run.nstepmax=12;run.noutput=1000", [12]),
     "ot2d_20x28_iso_visc_res": ("orszag-tang", "mesh.nx=20;mesh.ny=28;hydro.cIso=0.9;hydro.nu=0.01;MHD.eta=0.02;run.nstepmax=12;run.noutput=1000", [12]),
     "ot2d_16x24_rot_visc_res": ("orszag-tang", "mesh.nx=16;mesh.ny=24;MHD.omega0=0.4;hydro.nu=0.01;MHD.eta=0.02;run.nstepmax=12;run.noutput=1000", [12]),
+    # --- the fastest cell in the outermost interior layer: what the reference scans there, before (plain path) its ghosts are refilled.
+    # A blast of one cell's radius centred on the high corner of the box (dx = dy = dz), reflecting (1) and outflow (2) faces; for MHD
+    # the field loop, which sits on the origin of the coordinates: the box is moved so that the origin is its high corner, the loop is
+    # one cell wide, light (density_in) and strong (amplitude), the flow at rest (tests/test_oracle_golden.py asserts where the maximum lies)
+    "blast2d_corner_16x24_reflect": ("blast2d", "mesh.nx=16;mesh.ny=24;blast.center_x=1.0;blast.center_y=1.5;blast.radius=0.0625;mesh.boundary_xmin=1;mesh.boundary_xmax=1;mesh.boundary_ymin=1;mesh.boundary_ymax=1;run.nstepmax=5;run.noutput=100", [0, 5]),
+    "blast2d_corner_16x24_outflow": ("blast2d", "mesh.nx=16;mesh.ny=24;blast.center_x=1.0;blast.center_y=1.5;blast.radius=0.0625;mesh.boundary_xmin=2;mesh.boundary_xmax=2;mesh.boundary_ymin=2;mesh.boundary_ymax=2;run.nstepmax=5;run.noutput=100", [0, 5]),
+    "blast3d_corner_12x18x12_reflect": ("blast2d", "mesh.nx=12;mesh.ny=18;mesh.nz=12;blast.center_x=1.0;blast.center_y=1.5;blast.center_z=1.0;blast.radius=0.08;mesh.boundary_xmin=1;mesh.boundary_xmax=1;mesh.boundary_ymin=1;mesh.boundary_ymax=1;mesh.boundary_zmin=1;mesh.boundary_zmax=1;run.nstepmax=4;run.noutput=100", [0, 4]),
+    "blast3d_corner_12x18x12_outflow": ("blast2d", "mesh.nx=12;mesh.ny=18;mesh.nz=12;blast.center_x=1.0;blast.center_y=1.5;blast.center_z=1.0;blast.radius=0.08;mesh.boundary_xmin=2;mesh.boundary_xmax=2;mesh.boundary_ymin=2;mesh.boundary_ymax=2;mesh.boundary_zmin=2;mesh.boundary_zmax=2;run.nstepmax=4;run.noutput=100", [0, 4]),
+    "fieldloop2d_corner_24x12_reflect": ("mhd_fieldloop2d", "mesh.nx=24;mesh.ny=12;mesh.xmin=-2.0;mesh.xmax=0.0;mesh.ymin=-1.0;mesh.ymax=0.0;FieldLoop.radius=0.08;FieldLoop.density_in=0.05;FieldLoop.amplitude=3.0;FieldLoop.vflow=0.0;mesh.boundary_xmin=1;mesh.boundary_xmax=1;mesh.boundary_ymin=1;mesh.boundary_ymax=1;run.nstepmax=5;run.noutput=100", [0, 5]),
+    "fieldloop2d_corner_24x12_outflow": ("mhd_fieldloop2d", "mesh.nx=24;mesh.ny=12;mesh.xmin=-2.0;mesh.xmax=0.0;mesh.ymin=-1.0;mesh.ymax=0.0;FieldLoop.radius=0.08;FieldLoop.density_in=0.05;FieldLoop.amplitude=3.0;FieldLoop.vflow=0.0;mesh.boundary_xmin=2;mesh.boundary_xmax=2;mesh.boundary_ymin=2;mesh.boundary_ymax=2;run.nstepmax=5;run.noutput=100", [0, 5]),
     "sod2d_32x8": ("hydro_sod2d", "mesh.nx=32;mesh.ny=8;run.nstepmax=10;run.noutput=100", [0, 10]),
 }
 

@@ -98,18 +98,19 @@ bool periodic_xy(const rgpu_params& p) { return p.bc[0] == RGPU_BC_PERIODIC && p
 int hydro3d_sweep_scan(const rgpu_ctx* c) { return no_later_write(c->p, false) && rgpu_tiled::hydro3d_sweep_covers(c->g) && c->g.grav_on != 2 ? 1 : 0; }
 // hydro 2D (fused step or flat update) and the flat 3D update (RGPU_TILED=0, per-cell gravity field): whole-domain steps
 int hydro_flat_scan(const rgpu_ctx* c) { return no_later_write(c->p, false) ? RG_DT_SLOTS : 0; }
-// 2D MHD (fused step or flat update): on the rotating path (ghosts refilled before the reference scans) with four periodic faces,
-// whose refilled high faces are bit-identical copies
-int mhd2d_scan(const rgpu_ctx* c) {
-  return c->g.grav_on != 2 && no_later_write(c->p, true) && (!c->g.rot || periodic_xy(c->p)) ? RG_DT_SLOTS : 0;
-}
+// 2D MHD (fused step or flat update): the plain path only.  On the rotating path the reference refills the ghosts before it scans, and
+// no face type makes the refilled Bx on the high x face the value the CT update left there: the emf carries xPos (the shear terms), so
+// even the periodic image, one box length away, differs (a last-column cell that sets the time step showed it:
+// tests/test_cfl_plant_emu.py, orszag-tang with MHD.omega0)
+int mhd2d_scan(const rgpu_ctx* c) { return c->g.grav_on != 2 && no_later_write(c->p, true) && !c->g.rot ? RG_DT_SLOTS : 0; }
 // 3D MHD slab pieces (RGPU_CORE_SCAN): the field on the three high faces keeps its CT value -- always on the plain path (the reference
-// scans before the ghosts are refilled); on the rotating path when y, z are periodic (bit-identical copies) and x is periodic or the
-// shearing box (its fill skips the first outer Bx face).  A z face shared with a neighbour slab (RGPU_BC_COPY) counts as periodic.
+// scans before the ghosts are refilled); on the rotating path when y, z are periodic (bit-identical copies) and x is the shearing box
+// (its fill skips the first outer Bx face).  Not with periodic x faces: the emf of the high x face carries another xPos than its image's.
+// A z face shared with a neighbour slab (RGPU_BC_COPY) counts as periodic.
 int mhd3d_pieces_scan(const rgpu_ctx* c) {
   const auto& bc = c->p.bc;
   auto zok = [](int b) { return b == RGPU_BC_PERIODIC || b == RGPU_BC_COPY; };
-  const bool rot_ok = (bc[0] == RGPU_BC_PERIODIC || bc[0] == RGPU_BC_SHEARINGBOX) && bc[1] == bc[0] && bc[2] == RGPU_BC_PERIODIC &&
+  const bool rot_ok = bc[0] == RGPU_BC_SHEARINGBOX && bc[1] == RGPU_BC_SHEARINGBOX && bc[2] == RGPU_BC_PERIODIC &&
                       bc[3] == RGPU_BC_PERIODIC && zok(bc[4]) && zok(bc[5]);
   return c->g.grav_on != 2 && no_later_write(c->p, true) && (!c->g.rot || rot_ok) ? RG_DT_SLOTS : 0;
 }

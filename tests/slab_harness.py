@@ -42,8 +42,11 @@ from ramsesgpu_amd.solver import Solver, load_library
 
 
 class SlabRun:
-    def __init__(self, ini_path, overrides="", library=None, device="cuda", group=None, overlap=True):
+    def __init__(self, ini_path, overrides="", library=None, device="cuda", group=None, overlap=True, initial_state=None):
+        """initial_state: this slab's state [nbVar][ksize][jsize][isize] instead of the problem's initial condition (ghosts are filled
+        by init_simulation either way); None: the problem's own"""
         self.L = library or load_library()
+        self.initial_state = initial_state
         self.group = group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -72,7 +75,11 @@ class SlabRun:
     def init_simulation(self):
         """each rank builds its own slab of the initial condition (no scatter from rank 0)"""
         import numpy as np
-        hU = self.L.init_condition(self.ini_path, self.overrides, self.p)
+        if self.initial_state is None:
+            hU = self.L.init_condition(self.ini_path, self.overrides, self.p)
+        else:
+            hU = np.array(self.initial_state, dtype=np.float64)
+            assert hU.shape == tuple(self.p.shape), (hU.shape, tuple(self.p.shape))
         self.U[0].copy_(torch.from_numpy(np.ascontiguousarray(hU)))
         G = self.L.init_gravity(self.ini_path, self.overrides, self.p)   # this slab's planes of h_gravity, if the problem has one
         if G is not None:

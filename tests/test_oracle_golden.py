@@ -54,6 +54,35 @@ def test_rough_dissipative_fixtures_carry_a_stage_that_matters(name, product_lib
     assert 0.02 <= D.min() and D.max() <= 0.2, (name, D.min(), D.max())
 
 
+CORNER_FIXTURES = ["blast2d_corner_16x24_reflect", "blast2d_corner_16x24_outflow", "blast3d_corner_12x18x12_reflect", "blast3d_corner_12x18x12_outflow",
+                   "fieldloop2d_corner_24x12_reflect", "fieldloop2d_corner_24x12_outflow"]
+
+
+@pytest.mark.parametrize("name", CORNER_FIXTURES)
+def test_corner_fixtures_carry_their_fastest_cell_in_the_outermost_layer(name, oracle, product_lib):
+    """the fixtures that pin what the reference scans in its last interior layer (and when: before or after the ghost refill): in the
+    oracle's state after the first step -- whose scan reproduces the second dt, the reference's log to its printed digits -- replacing
+    the outermost high-side layer (i = nx - 1 or j = ny - 1 or k = nz - 1) by the low corner cell drops 1/dt to <= 0.8 of its value
+    (tests/cfl_plant_checks.py: masking_ratio, MASK_CAP)"""
+    import cfl_plant_checks as cp
+    import parity_checks as pc
+    case = golden_cases()[name]
+    p = product_lib.params_from_ini(ini(case["base"]), case["overrides"])
+    g = load_golden(name)
+    U0 = product_lib.init_condition(ini(case["base"]), case["overrides"], p)
+    U1, _, _ = oracle.run_sequential(p, U0, 1)
+    _, dts, _ = oracle.run_sequential(p, U0, 2)
+    assert p.cfl / oracle.compute_inv_dt(p, U1) == dts[1]
+    pc.assert_dt_log(dts, g["log_dt"], p, name)
+    gw = p.ghostWidth
+    nz = p.nz if p.three_d else 1
+    layer = [(k + gw if p.three_d else 0, j + gw, i + gw) for k in range(nz) for j in range(p.ny) for i in range(p.nx)
+             if i == p.nx - 1 or j == p.ny - 1 or (p.three_d and k == nz - 1)]
+    ratio = cp.masking_ratio(oracle, p, U1, layer, (gw if p.three_d else 0, gw, gw))
+    print("%s: 1/dt with the outermost high-side layer masked / unmasked = %.3f" % (name, ratio))
+    assert ratio <= cp.MASK_CAP, (name, ratio)
+
+
 @pytest.mark.parametrize("name", ["mri_8x16x8_history", "ot3d_12_history"])
 def test_oracle_history_matches_reference_history_file(name, oracle, product_lib):
     """the reference writes <prefix>_history.txt with 6 significant digits (MHDRunBase.cpp:3596-3602, 3401-3402): one
