@@ -346,6 +346,40 @@ int rgpu_run_steps(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, 
  * dt_log holds nsteps doubles or is NULL.  If a launch fails after some steps of a batch were queued, *nStep, *t, *dt (and dt_log)
  * are advanced for the steps that did run before the error is returned. */
 int rgpu_run_steps_log(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log);
+/* ... the same, with the history file's cadence inside (MHD, single domain): the loop of MHDRunGodunov.cpp:3975-3984,
+ *     n = 0
+ *     while n < nsteps and *t < tEnd:
+ *         if *tHist == 0 or ((*t - *dt <= *tHist + dtHist) and (*t > *tHist + dtHist)):
+ *             k = (*hist_n)++                      (hist_n starts at 0 in every call)
+ *             hist_step[k] = *nStep; hist_t[k] = *t; hist_dt[k] = *dt
+ *             hist[k][:] = rgpu_history_mri(c, *nStep % 2)
+ *             *tHist += dtHist
+ *         rgpu_one_step_integration(c, nStep, t, dt); n++
+ *     return n
+ * *nStep, *t, *dt, dt_log and the state advance exactly as in rgpu_run_steps_log; the sample steps and *tHist are those of the code
+ * above, evaluated in doubles with those expressions in that order; hist[k] holds, bit for bit, the eight doubles rgpu_history_mri of
+ * the same library returns on a lone context holding that state.  hist_step, hist_t, hist_dt hold nsteps entries, hist nsteps rows of
+ * RGPU_HIST_NQ; dt_log may be NULL.  The reference's quirks stay: dtHist == 0 with *tHist == 0 samples before every step, and a step
+ * that overshoots more than one interval can end the series.  A sample is taken only at the head of a turn that begins (*t < tEnd): the
+ * state after the last step of a call is sampled by the next call, so a run cut into calls gives the series of one call.
+ * Where the context takes its time step from the device (rgpu_device_time_step_ready: the 2D all-periodic MHD box; rgpu_clock_capable:
+ * 3D MHD, plain, rotating and shearing box) the decision, the row and *tHist += dtHist are formed on the device behind each tick of the
+ * batch (csrc/hip/history_batch.h: the kernels of rgpu_history_mri behind a gate, the host's small arithmetic in a finish kernel, a log
+ * of RGPU_CLOCK_BATCH records read back once per batch with the clock records -- allocated by the first call that needs it, not part of
+ * rgpu_device_bytes); every other configuration, and option "history_batch" = 0, takes the code above literally.
+ * Errors: RGPU_EUNSUPPORTED for a hydro context; RGPU_EINVAL for a slab context (slab_count > 1, as rgpu_history_mri), a NULL pointer
+ * among nStep, t, dt, tHist, hist_n, hist_step, hist_t, hist_dt, hist, or nsteps < 0.  When the call ends with a negative code, *hist_n
+ * counts only samples whose values were written, and *nStep, *t, *dt, *tHist describe the steps that ran; the head sample of the step
+ * that failed is among them on the literal path (it is taken before the step) and is not inside a device batch (the records behind
+ * the last step that ran are not read). */
+#define RGPU_HIST_NQ 8   /* the out[8] of rgpu_history_mri */
+int rgpu_run_steps_history(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log,
+                           double dtHist, double* tHist,          /* in / out */
+                           int* hist_n, int* hist_step /* [nsteps] */, double* hist_t /* [nsteps] */,
+                           double* hist_dt /* [nsteps] */, double* hist /* [nsteps][RGPU_HIST_NQ] */);
+/* how many heads of rgpu_run_steps_history this context has queued on the device so far (one per step of a device-clock batch,
+ * sampling or not; 0 where every call took the literal loop): lets a caller (and the tests) tell which path ran */
+long rgpu_history_batch_heads(rgpu_ctx* c);
 /* 1 when the next step of rgpu_run_steps on the state U[parity] would take its time step from the device (see above), else 0:
  * lets a caller (and the tests) tell which loop runs. */
 int rgpu_device_time_step_ready(rgpu_ctx* c, int parity);
@@ -557,6 +591,7 @@ int rgpu_selftest_alfven(const rgpu_params* p, int n, const double* states36, do
  *   "xcd_sub" (-1)      sub-band size (cells) of the XCD-aware workgroup order of the flat kernels, read by rgpu_create; 0: linear
  *   "zseg" (0)          planes per z segment of the tiled sweeps; 0: planned per launch
  *   "chunks" (-1)       chunks of the two-stream schedule of the flat 3D MHD kernels, read by rgpu_create; 1: one stream
+ *   "history_batch" (1) rgpu_run_steps_history samples on the device inside the device-clock batches; 0: its literal loop everywhere
  *   "member_params" (0) 1: the fused rounds of EVERY ensemble read their constants from the per-member table (the path of a
  *                       parameter scan), even when all sets are equal: the table path and the by-value path on one workload
  * rgpu_set_option returns the previous value (-1: unknown name; the options above are never negative except "as created"). */

@@ -137,16 +137,31 @@ int rgpu_clock_close(rgpu_ctx* c, int nStep0, int* ran, double* t, double* dt_la
   return RGPU_OK;
 }
 
+// what rgpu_run_steps_history adds to the loop: the history cadence and where the samples go (see include/rgpu.h)
+struct HistRun {
+  double dtHist; double* tHist;
+  int* n; int* step; double* t; double* dt; double* v;   // *n samples so far; step[k], t[k], dt[k], v[k][RGPU_HIST_NQ]
+  bool batch;                                            // option "history_batch": sample on the device inside the device-clock batches
+};
+static_assert((int)HIST_BATCH_NQ == RGPU_HIST_NQ, "include/rgpu.h states the width of a history row");
+
 // rgpu_run_steps_log; *why = 0, or the stop code of the record that ended the run (1: tEnd, 2: dt is not a number, 3: 1/dt is not
-// finite -- the last two are also reported as RGPU_EHIP)
-static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int* why) {
+// finite -- the last two are also reported as RGPU_EHIP).  H != 0: rgpu_run_steps_history
+static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int* why, const HistRun* H = 0) {
   *why = 0;
   int done = 0;
   struct Current { rgpu_ctx* c; const int* n; ~Current() { c->cur = *n & 1; } } current = {c, nStep};   // however the loop is left: U[*nStep % 2] is the state
   (void)current;
   while (done < nsteps && *t < tEnd) {
     const int parity = *nStep % 2;
-    if (!clock_ready(c, parity)) {   // the reference's loop body (the first step of a run always comes through here)
+    if (!clock_ready(c, parity) || (H && !H->batch)) {   // the reference's loop body (the first step of a run always comes through here)
+      if (H && hist_batch_due(*t, *dt, *H->tHist, H->dtHist)) {   // ... with the head of MHDRunGodunov.cpp:3975-3984, literally
+        const int k = *H->n;
+        if (const int rch = rgpu_history_mri(c, parity, H->v + (size_t)k * RGPU_HIST_NQ)) return rch;
+        H->step[k] = *nStep; H->t[k] = *t; H->dt[k] = *dt;
+        *H->n = k + 1;
+        *H->tHist += H->dtHist;
+      }
       const int rc = rgpu_one_step_integration(c, nStep, t, dt);
       if (rc) return rc;
       if (dt_log) dt_log[done] = *dt;
@@ -154,18 +169,28 @@ static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, doub
       continue;
     }
     const int m = (nsteps - done < rgpu_ctx::kClockBatch) ? nsteps - done : (int)rgpu_ctx::kClockBatch;
+    if (H && !c->d_hist) {    // the log of a batch and its pinned mirror: allocated by the first call that needs them
+      if (rg_malloc((void**)&c->d_hist, rgpu_ctx::kClockBatch * sizeof(HistBatchRec)) || rg_host_alloc((void**)&c->h_hist, rgpu_ctx::kClockBatch * sizeof(HistBatchRec))) {
+        if (c->d_hist) { rg_free(c->d_hist); c->d_hist = 0; }
+        c->h_hist = 0;
+        return RG_HIPFAIL(c, "run_steps_history: log of the batch");
+      }
+    }
     c->fold_request = true;
     const int rc_open = rgpu_clock_open(c, *t, tEnd);
     c->fold_request = false;
     if (rc_open) return rc_open;
     int queued = 0, rc = 0;
     const int n0 = *nStep;
+    const double dt0 = *dt;   // the loop's *dt at the head of the batch's first step
     for (; queued < m; ++queued) {
       if ((rc = rgpu_clock_tick(c)) != 0) break;
       if (stop_now(c)) { ++queued; break; }   // (host emulation: the record is already there and says the loop has ended)
       // == rgpu_godunov_unsplit for this configuration, every dt / t dependence read from the record on the device
       const int n = n0 + queued;
       if (!clock_ready(c, n % 2)) rc = RGPU_EHIP;   // (cannot happen: the step before left its CFL maxima and, in 2D, its ghost cells)
+      // the head of the turn: the history row of U[n % 2], taken on the device if the record and the log say so (hip/history_batch.h)
+      if (rc == 0 && H && history_batch_queue(c, n, queued, dt0, *H->tHist, H->dtHist)) rc = RGPU_EHIP;
       if (rc == 0) rc = (step_pre(c, n) || step_core(c, n, 0.0, 0.0) || step_post_a(c, n, 0.0, 0.0) || step_post_b(c, n)) ? RGPU_EHIP : 0;
       if (rc == 0 && !c->rec.slots((n + 1) % 2)) rc = RGPU_EHIP;   // (cannot happen: same configuration, same kernels)
       if (rc) { c->clk_n = queued; break; }   // the record of the step that failed to queue is not read back
@@ -174,10 +199,25 @@ static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, doub
     // advance nStep / t / dt for them before reporting, so that the caller's step count and parity describe the device state
     const std::string launch_err = rc ? c->err + " " + rg_last_error_string() : std::string();
     int ran = 0, stop = 0;
+    // the log travels with the clock records: queued behind them here, complete after the one synchronisation of rgpu_clock_close
+    const int nlog = H ? queued : 0;   // (a record behind the last head queued is copied unwritten and not read)
+    const bool log_ok = nlog == 0 || rg_copy_d2h(c->h_hist, c->d_hist, (size_t)nlog * sizeof(HistBatchRec), c->stream) == 0;
     const int rc2 = rgpu_clock_close(c, n0, &ran, t, dt, dt_log ? dt_log + done : 0, &stop);
     if (rc2) return rc2;
     *nStep += ran;
     done += ran;
+    if (H && ran > 0) {   // a step that ran had its head queued in front of it: records [0, ran) are written (ran <= nlog)
+      if (!log_ok || ran > nlog) { c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps_history: read-back of the log"); }
+      for (int r = 0; r < ran; ++r) {
+        const HistBatchRec& hr = c->h_hist[r];
+        if (!hr.sampled) continue;
+        const int k = *H->n;
+        H->step[k] = hr.step; H->t[k] = hr.t; H->dt[k] = hr.dt;
+        for (int q = 0; q < RGPU_HIST_NQ; ++q) H->v[(size_t)k * RGPU_HIST_NQ + q] = hr.v[q];
+        *H->n = k + 1;
+      }
+      *H->tHist = c->h_hist[ran - 1].tHist;
+    }
     if (rc) { c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps: queueing a device-clock step: " + launch_err); }
     if (ran < queued) {
       *why = stop;
@@ -197,6 +237,22 @@ int rgpu_run_steps_log(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double*
 
 int rgpu_run_steps(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt) {
   return rgpu_run_steps_log(c, nsteps, tEnd, nStep, t, dt, 0);
+}
+
+long rgpu_history_batch_heads(rgpu_ctx* c) { return c ? c->hist_heads : 0; }
+
+int rgpu_run_steps_history(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, double dtHist, double* tHist,
+                           int* hist_n, int* hist_step, double* hist_t, double* hist_dt, double* hist) {
+  RG_CHECK_CTX(c);
+  if (!nStep || !t || !dt || !tHist || !hist_n || !hist_step || !hist_t || !hist_dt || !hist) return fail(c, RGPU_EINVAL, "run_steps_history: null pointer");
+  *hist_n = 0;
+  if (!c->U[0]) return fail(c, RGPU_EINVAL, "run_steps_history: context without state");
+  if (!c->p.mhdEnabled) return fail(c, RGPU_EUNSUPPORTED, "run_steps_history: history diagnostics are defined for MHD runs");
+  if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, "run_steps_history: slab contexts take their history through the slab driver");
+  if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_history: nsteps is negative");
+  const HistRun H = {dtHist, tHist, hist_n, hist_step, hist_t, hist_dt, hist, rgpu::options().history_batch != 0};
+  int why = 0;
+  return run_steps_impl(c, nsteps, tEnd, nStep, t, dt, dt_log, &why, &H);
 }
 
 }  // extern "C"

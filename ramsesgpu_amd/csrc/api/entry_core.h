@@ -17,6 +17,8 @@ void rgpu_destroy(rgpu_ctx* c) {
   rg_free(c->d_red_base); rg_host_free(c->h_red);
   if (c->d_clk) rg_free(c->d_clk);
   if (c->h_clk) rg_host_free(c->h_clk);
+  if (c->d_hist) rg_free(c->d_hist);
+  if (c->h_hist) rg_host_free(c->h_hist);
   if (c->ev_ok) { rg_event_destroy(c->ev0); rg_event_destroy(c->ev1); }
   if (c->fork_ok) rg_event_destroy(c->ev_fork);
   for (int i = 0; i < c->n_order_events; ++i) { rg_event_destroy(c->ev_trace[i]); rg_event_destroy(c->ev_flux[i]); }
@@ -257,9 +259,7 @@ int rgpu_history_mri(rgpu_ctx* c, int parity, double* out) {
   const int is = c->g.isize, gw = c->g.gw;
   std::vector<double> cols((size_t)HIST_NQ * is), rcol(is), mvx(is), mvy(is);
   if (history_columns(c, parity, cols.data())) return RG_HIPFAIL(c, "history_mri");
-  double dTau = p.dx * p.dy;
-  if (c->g.three_d) dTau = p.dx * p.dy * p.dz / (p.xMax - p.xMin) / (p.yMax - p.yMin) / (p.zMax - p.zMin);   // MHDRunBase.cpp:3533-3536
-  else dTau = p.dx * p.dy / (p.xMax - p.xMin) / (p.yMax - p.yMin);                                         // :3351-3353
+  const double dTau = hist_dtau(c);
   const int nyz = p.ny * (c->g.three_d ? p.nz : 1);
   for (int i = 0; i < is; ++i) { mvx[i] = cols[(size_t)1 * is + i] / nyz; mvy[i] = cols[(size_t)2 * is + i] / nyz; }
   if (history_reynolds(c, parity, mvx.data(), mvy.data(), dTau, rcol.data())) return RG_HIPFAIL(c, "history_mri");

@@ -35,6 +35,42 @@ int history_reynolds(rgpu_ctx* c, int parity, const double* h_mean_vx, const dou
   return 0;
 }
 
+// the volume element of the history sums, normalised by the box (MHDRunBase.cpp:3533-3536; 2D: :3351-3353)
+double hist_dtau(const rgpu_ctx* c) {
+  const rgpu_params& p = c->p;
+  if (c->g.three_d) return p.dx * p.dy * p.dz / (p.xMax - p.xMin) / (p.yMax - p.yMin) / (p.zMax - p.zMin);
+  return p.dx * p.dy / (p.xMax - p.xMin) / (p.yMax - p.yMin);
+}
+
+// ---- the history row of a step inside a batch of device-clock steps (hip/history_batch.h) ---------------------------
+// Queues, behind the tick of the step `nStep` (record c->clk_cur, the `slot`-th of the open batch), the five launches that take the
+// row of rgpu_history_mri of U[nStep % 2] when the loop's condition holds for this step, and write d_hist[slot] either way.
+// dt0, tHist0: the loop's *dt and *tHist at the head of the batch's first step (read by slot 0 only).
+// Scratch in F exactly as hist_scratch lays it out (the Reynolds column sums go where the vx sums were).  F is dead here: the
+// step before is complete in stream order (a batch is queued on the context stream alone: mhd3d_core is `serial` while c->clk_cur
+// is set, the fused 2D step is one launch), and the first kernel of the step that follows which touches F -- the 3D sweep
+// (rgpu_tiled::mhd3d_sweep) -- writes every entry of F, emf that the shear remap and the update read; step_pre's ghost fill works on
+// U alone and the fused 2D step does not use F at all.  It is the liveness rgpu_history_mri between two steps has always relied on.
+int history_batch_queue(rgpu_ctx* c, int nStep, int slot, double dt0, double tHist0, double dtHist) {
+  const HistScratch h = hist_scratch(c);
+  const size_t is = (size_t)c->g.isize;
+  double* rcol = h.cols + is;   // column 1 (the vx sums) has served once the means are formed
+  const double* U = c->U[nStep & 1];
+  const HistBatchGate gate = {c->clk_cur, slot ? c->d_clk + slot - 1 : 0, slot ? c->d_hist + slot - 1 : 0, dt0, tHist0, dtHist};
+  const double dTau = hist_dtau(c);
+  const int nyz = c->p.ny * (c->g.three_d ? c->p.nz : 1);
+  K_hist_monitor_gated<K_hist_rows> k1 = {gate, {c->g, U, h.rows}};
+  K_hist_monitor_cols k2 = {gate, {c->g, h.rows, h.cols, HIST_NQ}, h.mean, nyz};
+  K_hist_monitor_gated<K_hist_reynolds> k3 = {gate, {c->g, U, h.mean, h.mean + is, dTau, h.rows}};
+  K_hist_monitor_gated<K_hist_cols> k4 = {gate, {c->g, h.rows, rcol, 1}};
+  K_hist_monitor_finish k5 = {gate, c->g.isize, c->g.gw, h.cols, rcol, dTau, nStep, c->d_hist + slot};
+  if (rg_launch<kBlock>(c->stream, (unsigned)h.R, k1) || rg_launch<kBlock>(c->stream, (unsigned)(HIST_NQ * is), k2) ||
+      rg_launch<kBlock>(c->stream, (unsigned)h.R, k3) || rg_launch<kBlock>(c->stream, (unsigned)is, k4) ||
+      rg_launch<64>(c->stream, (unsigned)HIST_BATCH_NQ, k5)) return -1;
+  ++c->hist_heads;
+  return 0;
+}
+
 // ---- the monitor of a 2D state (kernels_monitor.h; rgpu_state_monitor) ----------------------------------------------
 // Scratch in F like the history sums: the segment sums part[MON_NQ][nseg][nx], then the lane values [lanes][MON_NQ].  Steps 1 - 3 of
 // the summation order on the device, the butterfly over the lane values on the host (the same additions, mon_combine).  Reads the

@@ -575,11 +575,42 @@ void GodunovRun::restore_forcing_process(int nStep) {
 // problem none (history_empty); the turbulence problems get history_turbulence's twenty columns.  The sums come from the device
 // (rgpu_history_mri) instead of a copy of the state to the host.  The inertial-wave problem gets history_inertial_wave's
 // probe row (:3414-3469): the velocity of one cell in units of cIso, read with rgpu_read_cell.
+// Largest 3D box (cells) whose history the run loop takes through rgpu_run_steps_history: the largest size at which the batched call
+// was MEASURED to beat the per-step loop (the table's MRI 128 x 256 x 128 row; at 512^3 the two are level and
+// nothing in between was measured).  Move it with that table, not without.
+static const long long kHistoryBatchMaxCells = 128LL * 256 * 128;
+
+// which of the two rows built from rgpu_history_mri's eight sums a single-domain run of this problem writes
+int GodunovRun::history_row_kind() const {
+  if (!p_.mhdEnabled) return 0;
+  const std::string problem = cfg_.get_string("hydro", "problem", "unknown");
+  if (problem == "MRI" || problem == "Mri" || problem == "mri") return p_.nz_global == 1 ? 0 : 1;   // history_mri does nothing in 2D
+  return (problem == "Orszag-Tang" || problem == "OrszagTang") ? 2 : 0;
+}
+
+// the row itself (and, at t <= 0, the header in front of it): h = the out[8] of rgpu_history_mri taken at time t, dt the last time step
+void GodunovRun::write_history_row(bool mri, double t, double dt, const double* h) {
+  const std::string fileName = cfg_.get_string("output", "outputDir", "./") + "/" + cfg_.get_string("output", "outputPrefix", "output") +
+                               "_" + cfg_.get_string("history", "filename", "history.txt");
+  std::ofstream histo(fileName.c_str(), std::ios::out | std::ios::app | std::ios::ate);
+  if (t <= 0) {
+    histo << "# history" << std::endl;
+    if (mri) histo << "# totalTime dt mass maxwell reynolds maxwell+reynolds magp mean_Bx mean_By mean_Bz divB\n";
+    else histo << "# totalTime dt mass divB\n";
+  }
+  if (mri)
+    histo << t << "\t" << dt << "\t" << h[0] << "\t" << h[1] << "\t" << h[2] << "\t" << h[1] + h[2] << "\t" << h[3] << "\t"
+          << h[4] << "\t" << h[5] << "\t" << h[6] << "\t" << h[7] << "\n";
+  else
+    histo << t << "\t" << dt << "\t" << h[0] << "\t" << h[7] << "\n";
+}
+
 void GodunovRun::history(int nStep, double dt) {
   if (!p_.mhdEnabled) return;
   const std::string problem = cfg_.get_string("hydro", "problem", "unknown");
-  const bool mri = problem == "MRI" || problem == "Mri" || problem == "mri";
-  bool dflt = problem == "Orszag-Tang" || problem == "OrszagTang";
+  const int kind = history_row_kind();   // the one place that classifies the problem name (an MRI problem in 2D has no row: 0)
+  const bool mri = kind == 1;
+  bool dflt = kind == 2;
   if (slab()) {
     // z-slab runs follow the history set-up of the MPI classes (HydroRunBaseMpi.cpp:10667-10730): MRI -> history_mhd_mri,
     // turbulence -> history_mhd_turbulence (16 columns, no DFT amplitudes), every other MHD problem -> history_mhd_default
@@ -642,24 +673,11 @@ void GodunovRun::history(int nStep, double dt) {
     return;
   }
   if (!mri && !dflt) return;
-  if (mri && p_.nz_global == 1) return;   // history_mri does nothing in 2D
   double h[8];
   if (slab()) hook_check(hooks_.history_mri(hooks_.self, nStep % 2, h), "history");   // the same sums on every rank; rank 0 writes
   else check(rgpu_history_mri(ctx_, nStep % 2, h), "history");
   if (p_.slab_rank != 0) return;
-  const std::string fileName = cfg_.get_string("output", "outputDir", "./") + "/" + cfg_.get_string("output", "outputPrefix", "output") +
-                               "_" + cfg_.get_string("history", "filename", "history.txt");
-  std::ofstream histo(fileName.c_str(), std::ios::out | std::ios::app | std::ios::ate);
-  if (totalTime_ <= 0) {
-    histo << "# history" << std::endl;
-    if (mri) histo << "# totalTime dt mass maxwell reynolds maxwell+reynolds magp mean_Bx mean_By mean_Bz divB\n";
-    else histo << "# totalTime dt mass divB\n";
-  }
-  if (mri)
-    histo << totalTime_ << "\t" << dt << "\t" << h[0] << "\t" << h[1] << "\t" << h[2] << "\t" << h[1] + h[2] << "\t" << h[3] << "\t"
-          << h[4] << "\t" << h[5] << "\t" << h[6] << "\t" << h[7] << "\n";
-  else
-    histo << totalTime_ << "\t" << dt << "\t" << h[0] << "\t" << h[7] << "\n";
+  write_history_row(mri, totalTime_, dt, h);
 }
 
 int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
@@ -688,6 +706,16 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
   double tHist = totalTime_;   // MHDRunGodunov.cpp:3916
   // z-slab runs: the MRI / Orszag-Tang history goes through the slab driver's global sums; the other problems' do not
   const bool slab_history_ok = slab() && hooks_.history_mri;   // (every MHD problem has a history in the MPI classes)
+  // A single-domain run whose history row is the MRI or the default one takes its samples inside rgpu_run_steps_history: the turns up
+  // to the next log line or output are one call, the cadence above is evaluated there (on the device inside the device-clock
+  // batches) and the returned samples are written with the row writer of history().  The turbulence, inertial-wave and z-slab
+  // histories (other sums, a probe cell, global sums through the slab driver) keep the per-step loop below.  So do the classes of run
+  // where the batched call was not measured to beat that loop: 2D (the extra launches behind every tick cost what
+  // the host turn did) and 3D boxes above kHistoryBatchMaxCells, the largest size at which it won (at 512^3 the two are level).
+  const int history_kind = (historyEnabled && !hooked_ && !slab()) ? history_row_kind() : 0;
+  const bool history_batched = history_kind != 0 && p_.nz_global != 1 && (long long)p_.nx * p_.ny * p_.nz <= kHistoryBatchMaxCells;
+  std::vector<int> hist_step;
+  std::vector<double> hist_t, hist_dt, hist_v;
   const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   while (totalTime_ < rs_.tEnd && nStep < rs_.nStepmax) {
     if (rs_.nLog > 0 && (nStep % rs_.nLog) == 0 && p_.slab_rank == 0)
@@ -706,19 +734,25 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
       if (p_.slab_rank == 0) std::printf("  step=%9d t=%14.8f dt=%16.12f\n", nStep, totalTime_, dt);
     }
     if (historyEnabled && slab() && !slab_history_ok) note_once(&noted_hist_, "z-slab run: this problem's history file is not written");
-    if (historyEnabled && (!slab() || slab_history_ok) && (tHist == 0 || ((totalTime_ - dt <= tHist + dtHist) && (totalTime_ > tHist + dtHist)))) {
+    if (historyEnabled && !history_batched && (!slab() || slab_history_ok) && (tHist == 0 || ((totalTime_ - dt <= tHist + dtHist) && (totalTime_ > tHist + dtHist)))) {
       history(nStep, dt);
       tHist += dtHist;
     }
     // the turns of this loop up to the next one that logs, writes or records history do nothing but step: rgpu_run_steps runs them
     // (same states, same dt sequence; where a step is one fused kernel the time step stays on the device in between)
     int quiet = 1;
-    if ((!hooked_ || hooks_.run_steps) && !historyEnabled) {
+    if ((!hooked_ || hooks_.run_steps) && (!historyEnabled || history_batched)) {
       quiet = rs_.nStepmax - nStep;
       if (rs_.nLog > 0 && rs_.nLog - nStep % rs_.nLog < quiet) quiet = rs_.nLog - nStep % rs_.nLog;
       if (rs_.nOutput > 0 && rs_.nOutput - nStep % rs_.nOutput < quiet) quiet = rs_.nOutput - nStep % rs_.nOutput;
     }
-    if (quiet > 1) {
+    if (history_batched) {
+      int hn = 0;
+      if ((int)hist_step.size() < quiet) { hist_step.resize(quiet); hist_t.resize(quiet); hist_dt.resize(quiet); hist_v.resize((size_t)quiet * RGPU_HIST_NQ); }
+      const int rc = rgpu_run_steps_history(ctx_, quiet, rs_.tEnd, &nStep, &totalTime_, &dt, 0, dtHist, &tHist, &hn, hist_step.data(), hist_t.data(), hist_dt.data(), hist_v.data());
+      for (int k = 0; k < hn; ++k) write_history_row(history_kind == 1, hist_t[k], hist_dt[k], &hist_v[(size_t)k * RGPU_HIST_NQ]);
+      if (rc < 0) check(rc, "run_steps_history");
+    } else if (quiet > 1) {
       if (hooked_) {
         const int rc = hooks_.run_steps(hooks_.self, quiet, rs_.tEnd, &nStep, &totalTime_, &dt);
         if (rc < 0) hook_check(rc, "run_steps");

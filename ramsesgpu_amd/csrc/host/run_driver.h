@@ -53,6 +53,8 @@ class GodunovRun {
   void inputRestartUpscaled(const std::string& path, bool* ghosts_read);
   void save_forcing_process(int nStep);
   void restore_forcing_process(int nStep);
+  int history_row_kind() const;                          // 0: no MRI / default row for this problem, 1: history_mri's, 2: history_default's
+  void write_history_row(bool mri, double t, double dt, const double* h);   // one row of the MRI / default history file
   void history(int nStep, double dt);                     // [history] enabled=yes: <outputDir>/<outputPrefix>_history.txt
 
   const rgpu_params& params() const { return p_; }

@@ -14,6 +14,7 @@ struct Options {
   int xcd_sub = -1;       // sub-band size (cells) of the XCD-aware workgroup order of the flat kernels; -1: rgpu_create's default
   int zseg = 0;           // planes per z segment of the tiled sweeps; 0: planned per launch (tile_grid_plan)
   int chunks = -1;        // chunks of the two-stream schedule of the flat 3D MHD kernels; -1: ksize / 8; 1: one stream
+  int history_batch = 1;  // rgpu_run_steps_history samples on the device inside the device-clock batches (0: the literal loop everywhere)
   int member_params = 0;  // 1: the fused rounds of every ensemble read their constants from the per-member table (hip/ensemble_scan.h), equal sets or not
 };
 inline Options& options() { static Options o; return o; }
@@ -26,6 +27,7 @@ inline int* option_slot(const char* name) {
   if (!std::strcmp(name, "xcd_sub")) return &o.xcd_sub;
   if (!std::strcmp(name, "zseg")) return &o.zseg;
   if (!std::strcmp(name, "chunks")) return &o.chunks;
+  if (!std::strcmp(name, "history_batch")) return &o.history_batch;
   if (!std::strcmp(name, "member_params")) return &o.member_params;
   return 0;
 }

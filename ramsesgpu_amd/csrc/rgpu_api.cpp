@@ -17,6 +17,7 @@
 #include "launchers.h"
 #include "rg_options.h"
 #include "rg_tiled.h"   // LDS-tiled cooperative kernels of the backend (hip/rg_tiled.h)
+#include "hip/history_batch.h"   // the history row sampled inside a batch of device-clock steps (flat functors: any backend)
 
 using namespace rgpu;
 using namespace rgpu_dev;

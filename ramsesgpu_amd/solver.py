@@ -162,6 +162,7 @@ class Solver:
         self.nStep = 0
         self.totalTime = 0.0
         self.dt = 0.0
+        self.tHist = 0.0
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -301,10 +302,31 @@ class Solver:
         self.dt_log = [log[i] for i in range(done)]     # the time steps of this call, in order
         return done
 
+    def run_steps_history(self, nsteps, dtHist, tEnd=float("inf")):
+        """up to nsteps turns of the reference's time loop with its history cadence inside (rgpu_run_steps_history: before a step, when
+        tHist == 0 or the last step carried t past tHist + dtHist, the row of history_mri is taken and tHist += dtHist; inside the
+        device-clock batches decision and row are formed on the device, one read-back per batch).  tHist lives on the solver between
+        calls (start sets it to totalTime).  Returns (done, steps, t, dt, values[n, 8]): the steps done, and per sample the step number,
+        the time and the dt column of the history file, and the eight values in the order of HISTORY_NAMES"""
+        m = max(int(nsteps), 1)
+        n, t, d, th, hn = C.c_int(self.nStep), C.c_double(self.totalTime), C.c_double(self.dt), C.c_double(self.tHist), C.c_int(0)
+        log = (C.c_double * m)()
+        hstep, ht, hdt, hv = np.zeros(m, dtype=np.intc), np.zeros(m), np.zeros(m), np.zeros((m, 8))
+        done = self.lib.rgpu_run_steps_history(self.ctx, int(nsteps), float(tEnd), C.byref(n), C.byref(t), C.byref(d), log, float(dtHist), C.byref(th), C.byref(hn),
+                                               hstep.ctypes.data_as(C.POINTER(C.c_int)), ht.ctypes.data_as(_capi.c_double_p), hdt.ctypes.data_as(_capi.c_double_p),
+                                               hv.ctypes.data_as(_capi.c_double_p))
+        if done < 0:
+            self._chk(done, "run_steps_history")
+        self.nStep, self.totalTime, self.dt, self.tHist = n.value, t.value, d.value, th.value
+        self.dt_log = [log[i] for i in range(done)]
+        k = hn.value
+        return done, hstep[:k].copy(), ht[:k].copy(), hdt[:k].copy(), hv[:k].copy()
+
     def start(self, hU, nStepmax, tEnd=float("inf")):
         """init part + time loop of start() (MHDRunGodunov.cpp:3801-3989) without outputs; returns the dt list"""
         self.upload(hU, both=False)
         self.nStep, self.totalTime = 0, 0.0
+        self.tHist = self.totalTime   # MHDRunGodunov.cpp:3916
         self.make_all_boundaries(0, 0.0, 0.0)
         # h_U.copyTo(h_U2)
         self.upload(self.getDataHost(0), both=True)
