@@ -364,7 +364,7 @@ int rgpu_run_steps_log(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double*
  * state after the last step of a call is sampled by the next call, so a run cut into calls gives the series of one call.
  * Where the context takes its time step from the device (rgpu_device_time_step_ready: the 2D all-periodic MHD box; rgpu_clock_capable:
  * 3D MHD, plain, rotating and shearing box) the decision, the row and *tHist += dtHist are formed on the device behind each tick of the
- * batch (csrc/hip/history_batch.h: the kernels of rgpu_history_mri behind a gate, the host's small arithmetic in a finish kernel, a log
+ * batch (csrc/kernels_history.h: the kernels of rgpu_history_mri behind a gate, the host's small arithmetic in a finish kernel, a log
  * of RGPU_CLOCK_BATCH records read back once per batch with the clock records -- allocated by the first call that needs it, not part of
  * rgpu_device_bytes); every other configuration, and option "history_batch" = 0, takes the code above literally.
  * Errors: RGPU_EUNSUPPORTED for a hydro context; RGPU_EINVAL for a slab context (slab_count > 1, as rgpu_history_mri), a NULL pointer

@@ -1,6 +1,11 @@
 // api/ctx.h -- the context of the C ABI (struct rgpu_ctx), parameter validation, allocation, creation.  Part of the ONE translation
-// unit rgpu_api.cpp (included there, in this order: ctx, boundaries, step, history, then the entry points).
+// unit rgpu_api.cpp (included there, in this order: ctx, boundaries, step, history, monitor, forcing, then the entry points).
 #pragma once
+// every entry point makes the context's device current: a multi-GPU process (or a thread whose current device differs)
+// would otherwise launch on the wrong device
+#define RG_CHECK_CTX(c) do { if (!(c)) return RGPU_EINVAL; if ((c)->device >= 0) rg_set_device((c)->device); } while (0)
+#define RG_HIPFAIL(c, what) fail((c), RGPU_EHIP, std::string(what) + ": " + rg_last_error_string())
+
 namespace {
 const int kBlock = 256;      // streaming kernels
 const int kBlockHeavy = 64;  // Riemann kernels: 256 VGPRs, one wave per workgroup places best (64: 61.8, 128: 62.6, 256: 71.4 ms/step)
@@ -64,7 +69,7 @@ struct rgpu_ctx {
   StepClock* d_clk; StepClock* h_clk; const StepClock* clk_cur;
   int clk_n;                    // records queued in the open batch (rgpu_clock_open .. rgpu_clock_close), -1: no batch open
   double clk_t0, clk_tEnd;
-  // the history rows sampled inside a batch (hip/history_batch.h; rgpu_run_steps_history): one record per step of a batch on the device /
+  // the history rows sampled inside a batch (kernels_history.h; rgpu_run_steps_history): one record per step of a batch on the device /
   // in pinned host memory, allocated by the first call that needs them
   HistBatchRec* d_hist; HistBatchRec* h_hist;
   long hist_heads;              // history heads queued on the device so far (rgpu_history_batch_heads: lets a caller tell which path ran)

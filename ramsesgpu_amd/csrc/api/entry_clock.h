@@ -189,7 +189,7 @@ static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, doub
       // == rgpu_godunov_unsplit for this configuration, every dt / t dependence read from the record on the device
       const int n = n0 + queued;
       if (!clock_ready(c, n % 2)) rc = RGPU_EHIP;   // (cannot happen: the step before left its CFL maxima and, in 2D, its ghost cells)
-      // the head of the turn: the history row of U[n % 2], taken on the device if the record and the log say so (hip/history_batch.h)
+      // the head of the turn: the history row of U[n % 2], taken on the device if the record and the log say so (kernels_history.h)
       if (rc == 0 && H && history_batch_queue(c, n, queued, dt0, *H->tHist, H->dtHist)) rc = RGPU_EHIP;
       if (rc == 0) rc = (step_pre(c, n) || step_core(c, n, 0.0, 0.0) || step_post_a(c, n, 0.0, 0.0) || step_post_b(c, n)) ? RGPU_EHIP : 0;
       if (rc == 0 && !c->rec.slots((n + 1) % 2)) rc = RGPU_EHIP;   // (cannot happen: same configuration, same kernels)

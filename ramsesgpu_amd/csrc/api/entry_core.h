@@ -255,23 +255,14 @@ int rgpu_history_mri(rgpu_ctx* c, int parity, double* out) {
   if (!out || !c->U[0]) return fail(c, RGPU_EINVAL, "history_mri: null pointer / context without state");
   if (!c->p.mhdEnabled) return fail(c, RGPU_EUNSUPPORTED, "history diagnostics are defined for MHD runs");
   if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, "slab contexts: combine rgpu_history_columns / _reynolds across ranks");
-  const rgpu_params& p = c->p;
   const int is = c->g.isize, gw = c->g.gw;
   std::vector<double> cols((size_t)HIST_NQ * is), rcol(is), mvx(is), mvy(is);
   if (history_columns(c, parity, cols.data())) return RG_HIPFAIL(c, "history_mri");
-  const double dTau = hist_dtau(c);
-  const int nyz = p.ny * (c->g.three_d ? p.nz : 1);
-  for (int i = 0; i < is; ++i) { mvx[i] = cols[(size_t)1 * is + i] / nyz; mvy[i] = cols[(size_t)2 * is + i] / nyz; }
+  const double dTau = rgpu_hist::dtau(c->p);
+  const int nyz = c->p.ny * (c->g.three_d ? c->p.nz : 1);
+  for (int i = 0; i < is; ++i) { mvx[i] = rgpu_hist::yz_mean(cols[(size_t)1 * is + i], nyz); mvy[i] = rgpu_hist::yz_mean(cols[(size_t)2 * is + i], nyz); }
   if (history_reynolds(c, parity, mvx.data(), mvy.data(), dTau, rcol.data())) return RG_HIPFAIL(c, "history_mri");
-  double sum[HIST_NQ], reyn = 0.0;
-  for (int q = 0; q < HIST_NQ; ++q) { sum[q] = 0.0; for (int i = gw; i < is - gw; ++i) sum[q] += cols[(size_t)q * is + i]; }
-  for (int i = gw; i < is - gw; ++i) reyn += rcol[i];
-  out[0] = sum[0] * dTau;         // mass
-  out[1] = sum[4] * dTau;         // maxwell
-  out[2] = reyn;                  // reynolds (dTau is inside the sum, as in the reference)
-  out[3] = sum[3] * dTau / 2.;    // magp
-  out[4] = sum[5] * dTau; out[5] = sum[6] * dTau; out[6] = sum[7] * dTau;   // mean B
-  out[7] = sum[8];                // divB
+  for (int q = 0; q < rgpu_hist::NROW; ++q) out[q] = rgpu_hist::mri_row_value(q, cols.data(), rcol.data(), is, gw, dTau);
   return RGPU_OK;
 }
 
@@ -282,16 +273,9 @@ int rgpu_history_turbulence_sums(rgpu_ctx* c, int parity, double* s) {
   if (!s || !c->U[0]) return fail(c, RGPU_EINVAL, "history_turbulence: null pointer / context without state");
   if (!c->p.mhdEnabled || !c->g.three_d) return fail(c, RGPU_EUNSUPPORTED, "history_turbulence is defined for 3D MHD runs (it does nothing in 2D)");
   const int is = c->g.isize, gw = c->g.gw;
-  // rows [NQ][nz][isize] and columns [NQ][isize] in the flux array, dead between steps (F has 15 components per cell)
-  const size_t R = (size_t)is * c->g.nz;
-  double* rows = c->F;
-  double* cols = c->F + (size_t)HIST_TURB_NQ * R;
-  K_hist_turb_rows kr = {c->g, c->U[parity & 1], rows};
-  K_hist_cols kc = {c->g, rows, cols, HIST_TURB_NQ};
   std::vector<double> h((size_t)HIST_TURB_NQ * is);
-  if (rg_launch<kBlock>(c->stream, (unsigned)R, kr) || rg_launch<kBlock>(c->stream, (unsigned)(HIST_TURB_NQ * is), kc) ||
-      rg_copy_d2h(h.data(), cols, sizeof(double) * h.size(), c->stream) || rg_stream_sync(c->stream)) return RG_HIPFAIL(c, "history_turbulence");
-  for (int q = 0; q < HIST_TURB_NQ; ++q) { s[q] = 0.0; for (int i = gw; i < is - gw; ++i) s[q] += h[(size_t)q * is + i]; }
+  if (history_turbulence_columns(c, parity, h.data())) return RG_HIPFAIL(c, "history_turbulence");
+  for (int q = 0; q < HIST_TURB_NQ; ++q) s[q] = rgpu_hist::interior_sum(h.data() + (size_t)q * is, is, gw);
   return RGPU_OK;
 }
 
@@ -302,7 +286,7 @@ int rgpu_history_turbulence(rgpu_ctx* c, int parity, double* out) {
   double s[HIST_TURB_NQ];
   if (const int rc = rgpu_history_turbulence_sums(c, parity, s)) return rc;
   const rgpu_params& p = c->p;
-  const double dTau = p.dx * p.dy * p.dz / (p.xMax - p.xMin) / (p.yMax - p.yMin) / (p.zMax - p.zMin);
+  const double dTau = rgpu_hist::dtau(p);   // (3D: rgpu_history_turbulence_sums refuses a 2D context)
   const double pi = 2 * std::asin(1.0);
   const double mass = s[0] * dTau, eKin = s[1] * dTau, mean_v2 = s[2] * dTau, eMag = s[3] * dTau, helicity = s[4] * dTau;
   const double mBx = s[5] * dTau, mBy = s[6] * dTau, mBz = s[7] * dTau;

@@ -1,5 +1,36 @@
 // api/entry_misc.h -- entry points: synchronisation, phase timers, names, the self-tests of the device arithmetic, options.
 #pragma once
+namespace {
+// the functors of the two self-tests below (rgpu_selftest_arith, rgpu_selftest_alfven)
+struct K_selftest_arith {
+  const double* num; const double* den; double* quot; double* quot2; double* root; double* root2;
+  RG_DEVFN void operator()(unsigned i) const {
+    quot[i] = rg_div(num[i], rg_recip(den[i]));
+    quot2[i] = num[i] / den[i];
+    root[i] = rg_sqrt(num[i]);
+    root2[i] = sqrt(num[i]);
+  }
+};
+
+// one sample = the four corner states of an edge (LL, RL, LR, RR: r p u v w a b c each) and their four electric fields, SoA: in[q * n + i]
+struct K_selftest_alfven {
+  DevParams g; const double* in; double* e_sel; double* e_ref; int* route; unsigned n;
+  RG_DEVFN void operator()(unsigned i) const {
+    Prim8 s[4];
+    for (int q = 0; q < 4; ++q) {
+      const double* x = in + (size_t)(8 * q) * n + i;
+      s[q].r = x[0]; s[q].p = x[n]; s[q].u = x[2 * (size_t)n]; s[q].v = x[3 * (size_t)n]; s[q].w = x[4 * (size_t)n];
+      s[q].a = x[5 * (size_t)n]; s[q].b = x[6 * (size_t)n]; s[q].c = x[7 * (size_t)n];
+    }
+    const double E0 = in[(size_t)32 * n + i], E1 = in[(size_t)33 * n + i], E2 = in[(size_t)34 * n + i], E3 = in[(size_t)35 * n + i];
+    int r = 0;
+    e_sel[i] = mag_hlld_2d<false>(g, s[0], s[1], s[2], s[3], E0, E1, E2, E3, &r);
+    e_ref[i] = mag_hlld_2d<true>(g, s[0], s[1], s[2], s[3], E0, E1, E2, E3);
+    route[i] = r;
+  }
+};
+}  // namespace
+
 extern "C" {
 int rgpu_synchronize(rgpu_ctx* c) {
   RG_CHECK_CTX(c);

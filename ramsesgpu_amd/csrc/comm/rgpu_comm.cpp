@@ -18,6 +18,7 @@
 
 #include "rg_transport.h"
 #include "halo_ops.h"
+#include "../history_row.h"   // the arithmetic of the history rows behind the column sums (shared with librgpu)
 
 using rgpu_transport::P2P;
 
@@ -476,23 +477,17 @@ int rgpu_comm_history_mri(rgpu_comm* cm, int parity, double* out) {
   if (!out) return fail(cm, RGPU_EINVAL, "history_mri: null pointer");
   const rgpu_params& p = cm->p;
   if (!p.mhdEnabled) return fail(cm, RGPU_EUNSUPPORTED, "history diagnostics are defined for MHD runs");
-  const int gw = p.ghostWidth, is = p.nx + 2 * gw, NQ = 9;
+  const int gw = p.ghostWidth, is = p.nx + 2 * gw, NQ = rgpu_hist::NCOL;
   std::vector<double> cols((size_t)NQ * is), rcol(is), mvx(is), mvy(is);
   RG_TRY(rgpu_history_columns(cm->ctx, parity, cols.data()), "history_columns");
   void* s = rgpu_stream_handle(cm->ctx);
   if (cm->nranks > 1 && rgpu_transport::allreduce_sum_host(cm->tc, cols.data(), NQ * is, s)) return tr_fail(cm, "allreduce(history columns)");
-  const bool three_d = p.nz_global != 1;
-  const double dTau = three_d ? p.dx * p.dy * p.dz / (p.xMax - p.xMin) / (p.yMax - p.yMin) / (p.zMax - p.zMin)
-                              : p.dx * p.dy / (p.xMax - p.xMin) / (p.yMax - p.yMin);
-  const double nyz = (double)p.ny * (three_d ? p.nz_global : 1);
-  for (int i = 0; i < is; ++i) { mvx[i] = cols[(size_t)1 * is + i] / nyz; mvy[i] = cols[(size_t)2 * is + i] / nyz; }
+  const double dTau = rgpu_hist::dtau(p);
+  const double nyz = (double)p.ny * (p.nz_global != 1 ? p.nz_global : 1);   // of the whole box
+  for (int i = 0; i < is; ++i) { mvx[i] = rgpu_hist::yz_mean(cols[(size_t)1 * is + i], nyz); mvy[i] = rgpu_hist::yz_mean(cols[(size_t)2 * is + i], nyz); }
   RG_TRY(rgpu_history_reynolds(cm->ctx, parity, mvx.data(), mvy.data(), dTau, rcol.data()), "history_reynolds");
   if (cm->nranks > 1 && rgpu_transport::allreduce_sum_host(cm->tc, rcol.data(), is, s)) return tr_fail(cm, "allreduce(history reynolds)");
-  double sum[9], reyn = 0.0;
-  for (int q = 0; q < NQ; ++q) { sum[q] = 0.0; for (int i = gw; i < is - gw; ++i) sum[q] += cols[(size_t)q * is + i]; }
-  for (int i = gw; i < is - gw; ++i) reyn += rcol[i];
-  out[0] = sum[0] * dTau; out[1] = sum[4] * dTau; out[2] = reyn; out[3] = sum[3] * dTau / 2.;
-  out[4] = sum[5] * dTau; out[5] = sum[6] * dTau; out[6] = sum[7] * dTau; out[7] = sum[8];
+  for (int q = 0; q < rgpu_hist::NROW; ++q) out[q] = rgpu_hist::mri_row_value(q, cols.data(), rcol.data(), is, gw, dTau);
   return RGPU_OK;
 }
 
@@ -502,7 +497,7 @@ int rgpu_comm_history_turbulence(rgpu_comm* cm, int parity, double* out) {
   const rgpu_params& p = cm->p;
   double s[18];
   RG_TRY(rgpu_history_turbulence_sums(cm->ctx, parity, s), "history_turbulence_sums");
-  const double dTau = p.dx * p.dy * p.dz / (p.xMax - p.xMin) / (p.yMax - p.yMin) / (p.zMax - p.zMin);   // zMax - zMin: the whole box
+  const double dTau = rgpu_hist::dtau(p);   // zMax - zMin: the whole box (3D: the sums above refuse a 2D context)
   // this rank's values, scaled like the reference does before its MPI_Reduce calls
   const double mass = s[0] * dTau, eKin = s[1] * dTau, mean_v2 = s[2] * dTau, eMag = s[3] * dTau, helicity = s[4] * dTau, divB = s[17];
   const double mB[3] = {s[5] * dTau, s[6] * dTau, s[7] * dTau}, mrv[3] = {s[8] * dTau, s[9] * dTau, s[10] * dTau};

@@ -588,16 +588,23 @@ int GodunovRun::history_row_kind() const {
   return (problem == "Orszag-Tang" || problem == "OrszagTang") ? 2 : 0;
 }
 
-// the row itself (and, at t <= 0, the header in front of it): h = the out[8] of rgpu_history_mri taken at time t, dt the last time step
-void GodunovRun::write_history_row(bool mri, double t, double dt, const double* h) {
-  const std::string fileName = cfg_.get_string("output", "outputDir", "./") + "/" + cfg_.get_string("output", "outputPrefix", "output") +
-                               "_" + cfg_.get_string("history", "filename", "history.txt");
+// The history file, open for appending.  At t <= 0, the first row of a run, "# history" goes in first, followed by the line that names
+// the row's columns where the row has one.
+static std::ofstream open_history(const IniConfig& cfg, double t, const char* columns) {
+  const std::string fileName = cfg.get_string("output", "outputDir", "./") + "/" + cfg.get_string("output", "outputPrefix", "output") +
+                               "_" + cfg.get_string("history", "filename", "history.txt");
   std::ofstream histo(fileName.c_str(), std::ios::out | std::ios::app | std::ios::ate);
   if (t <= 0) {
     histo << "# history" << std::endl;
-    if (mri) histo << "# totalTime dt mass maxwell reynolds maxwell+reynolds magp mean_Bx mean_By mean_Bz divB\n";
-    else histo << "# totalTime dt mass divB\n";
+    histo << columns;
   }
+  return histo;
+}
+
+// the row itself (and, at t <= 0, the header in front of it): h = the out[8] of rgpu_history_mri taken at time t, dt the last time step
+void GodunovRun::write_history_row(bool mri, double t, double dt, const double* h) {
+  std::ofstream histo = open_history(cfg_, t, mri ? "# totalTime dt mass maxwell reynolds maxwell+reynolds magp mean_Bx mean_By mean_Bz divB\n"
+                                                  : "# totalTime dt mass divB\n");
   if (mri)
     histo << t << "\t" << dt << "\t" << h[0] << "\t" << h[1] << "\t" << h[2] << "\t" << h[1] + h[2] << "\t" << h[3] << "\t"
           << h[4] << "\t" << h[5] << "\t" << h[6] << "\t" << h[7] << "\n";
@@ -619,13 +626,7 @@ void GodunovRun::history(int nStep, double dt) {
       double h[14];
       hook_check(hooks_.history_turbulence(hooks_.self, nStep % 2, h), "history");   // collective; rank 0's values are the row
       if (p_.slab_rank != 0) return;
-      const std::string fileName = cfg_.get_string("output", "outputDir", "./") + "/" + cfg_.get_string("output", "outputPrefix", "output") +
-                                   "_" + cfg_.get_string("history", "filename", "history.txt");
-      std::ofstream histo(fileName.c_str(), std::ios::out | std::ios::app | std::ios::ate);
-      if (totalTime_ <= 0) {
-        histo << "# history" << std::endl;
-        histo << "# totalTime dt mass divB eKin eMag helicity mean_B mean_Bx mean_By mean_Bz mean_rhovx mean_rhovy mean_rhovz Ma_s Ma_alfven\n";
-      }
+      std::ofstream histo = open_history(cfg_, totalTime_, "# totalTime dt mass divB eKin eMag helicity mean_B mean_Bx mean_By mean_Bz mean_rhovx mean_rhovy mean_rhovz Ma_s Ma_alfven\n");
       histo << totalTime_ << "\t" << dt;
       for (int q = 0; q < 14; ++q) histo << "\t" << h[q];
       histo << "\n";
@@ -640,10 +641,7 @@ void GodunovRun::history(int nStep, double dt) {
     const int iPos = p_.ghostWidth + p_.nx / 2, kPos = p_.ghostWidth;
     if (p_.nz_global == 1) check(rgpu_read_cell(ctx_, nStep % 2, iPos, kPos, 0, u), "history");
     else check(rgpu_read_cell(ctx_, nStep % 2, iPos, 1, kPos, u), "history");
-    const std::string fileName = cfg_.get_string("output", "outputDir", "./") + "/" + cfg_.get_string("output", "outputPrefix", "output") +
-                                 "_" + cfg_.get_string("history", "filename", "history.txt");
-    std::ofstream histo(fileName.c_str(), std::ios::out | std::ios::app | std::ios::ate);
-    if (totalTime_ <= 0) histo << "# history" << std::endl;
+    std::ofstream histo = open_history(cfg_, totalTime_, "");   // (this row has no line of column names)
     const double rho = u[RGPU_ID], dvx = u[RGPU_IU] / rho, dvy = u[RGPU_IV] / rho;
     // the reference's row, missing separator between totalTime and dt included; fmt() = " " + setw(12) fixed, 8 digits
     histo << totalTime_ << "" << dt << " " << rho << " ";
@@ -660,13 +658,7 @@ void GodunovRun::history(int nStep, double dt) {
     if (p_.nz_global == 1) return;
     double h[18];
     check(rgpu_history_turbulence(ctx_, nStep % 2, h), "history");
-    const std::string fileName = cfg_.get_string("output", "outputDir", "./") + "/" + cfg_.get_string("output", "outputPrefix", "output") +
-                                 "_" + cfg_.get_string("history", "filename", "history.txt");
-    std::ofstream histo(fileName.c_str(), std::ios::out | std::ios::app | std::ios::ate);
-    if (totalTime_ <= 0) {
-      histo << "# history" << std::endl;
-      histo << "# totalTime dt mass divB eKin eMag helicity mean_rho mean_B mean_Bx mean_By mean_Bz mean_rhovx mean_rhovy mean_rhovz Ma_s Ma_alfven coef_x coef_y coef_z\n";
-    }
+    std::ofstream histo = open_history(cfg_, totalTime_, "# totalTime dt mass divB eKin eMag helicity mean_rho mean_B mean_Bx mean_By mean_Bz mean_rhovx mean_rhovy mean_rhovz Ma_s Ma_alfven coef_x coef_y coef_z\n");
     histo << totalTime_ << "\t" << dt;
     for (int q = 0; q < 18; ++q) histo << "\t" << h[q];
     histo << "\n";
@@ -704,6 +696,8 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
   const bool historyEnabled = p_.mhdEnabled && cfg_.get_bool("history", "enabled", false);
   const double dtHist = cfg_.get_float("history", "dtHist", static_cast<float>(10 * dt));
   double tHist = totalTime_;   // MHDRunGodunov.cpp:3916
+  // the head of a turn of the time loop takes a history row (MHDRunGodunov.cpp:3975-3984)
+  const auto history_due = [&]() { return tHist == 0 || ((totalTime_ - dt <= tHist + dtHist) && (totalTime_ > tHist + dtHist)); };
   // z-slab runs: the MRI / Orszag-Tang history goes through the slab driver's global sums; the other problems' do not
   const bool slab_history_ok = slab() && hooks_.history_mri;   // (every MHD problem has a history in the MPI classes)
   // A single-domain run whose history row is the MRI or the default one takes its samples inside rgpu_run_steps_history: the turns up
@@ -734,7 +728,7 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
       if (p_.slab_rank == 0) std::printf("  step=%9d t=%14.8f dt=%16.12f\n", nStep, totalTime_, dt);
     }
     if (historyEnabled && slab() && !slab_history_ok) note_once(&noted_hist_, "z-slab run: this problem's history file is not written");
-    if (historyEnabled && !history_batched && (!slab() || slab_history_ok) && (tHist == 0 || ((totalTime_ - dt <= tHist + dtHist) && (totalTime_ > tHist + dtHist)))) {
+    if (historyEnabled && !history_batched && (!slab() || slab_history_ok) && history_due()) {
       history(nStep, dt);
       tHist += dtHist;
     }

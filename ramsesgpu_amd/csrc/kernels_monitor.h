@@ -19,7 +19,7 @@
 //   eint = (E - ekin) - emag
 //   t[0..9] = rho, mx, my, mz, E, ekin, emag | rho, eint | divb
 // The high faces of the last interior row / column are in the first ghost layer and carry their constrained-transport value
-// after every step and after a ghost fill (hist_row_cell, kernels_bc.h, reads the same faces): no ghost fill is needed.
+// after every step and after a ghost fill (hist_row_cell, kernels_history.h, reads the same faces): no ghost fill is needed.
 //
 // Summation order of a sum over the nx x ny interior cells, ii = i - gw in [0, nx), jj = j - gw in [0, ny); every accumulator
 // starts at +0.0 and takes "a = a + x" in the order given:

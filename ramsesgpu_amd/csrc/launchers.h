@@ -3,6 +3,7 @@
 #pragma once
 #include "kernels_bc.h"
 #include "kernels_dissipative.h"
+#include "kernels_history.h"      // history diagnostics: row / column sums, their functors, the row inside a batch
 #include "kernels_hydro.h"
 #include "kernels_mhd2d.h"
 #include "kernels_mhd3d.h"
@@ -149,25 +150,9 @@ struct K_resist_eflux {
   DevParams g; const double* U; double* Fd; double eta, dt;
   RG_DEVFN void operator()(unsigned idx) const { resist_eflux_cell<ND>(g, U, Fd, eta, dt, idx); }
 };
-struct K_hist_rows {
-  DevParams g; const double* U; double* rows;
-  RG_DEVFN void operator()(unsigned idx) const { hist_row_cell(g, U, rows, idx); }
-};
-struct K_hist_turb_rows {
-  DevParams g; const double* U; double* rows;
-  RG_DEVFN void operator()(unsigned idx) const { hist_turb_row_cell(g, U, rows, idx); }
-};
-struct K_hist_cols {
-  DevParams g; const double* rows; double* cols; int nq;
-  RG_DEVFN void operator()(unsigned idx) const { hist_col_cell(g, rows, cols, nq, idx); }
-};
 struct K_checksum_rows {
   DevParams g; const double* U; unsigned long long* rows;
   RG_DEVFN void operator()(unsigned idx) const { checksum_row_cell(g, U, rows, idx); }
-};
-struct K_hist_reynolds {
-  DevParams g; const double* U; const double* mean_vx; const double* mean_vy; double dTau; double* rows;
-  RG_DEVFN void operator()(unsigned idx) const { hist_reynolds_cell(g, U, mean_vx, mean_vy, dTau, rows, idx); }
 };
 struct K_mhd_trace2d {
   DevParams g; const double* U; const double* Q; double* T; double dtdx, dtdy;

@@ -17,7 +17,6 @@
 #include "launchers.h"
 #include "rg_options.h"
 #include "rg_tiled.h"   // LDS-tiled cooperative kernels of the backend (hip/rg_tiled.h)
-#include "hip/history_batch.h"   // the history row sampled inside a batch of device-clock steps (flat functors: any backend)
 
 using namespace rgpu;
 using namespace rgpu_dev;
@@ -26,6 +25,8 @@ using namespace rgpu_dev;
 #include "api/boundaries.h"
 #include "api/step.h"
 #include "api/history.h"
+#include "api/monitor.h"
+#include "api/forcing.h"
 #include "api/entry_core.h"
 #include "api/entry_clock.h"
 #include "api/entry_ensemble.h"

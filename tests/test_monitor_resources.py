@@ -63,4 +63,4 @@ def test_every_other_kernel_is_as_it_was(lib_resources):
         assert k in now, "kernel %s is gone from %s" % (k, name)
         assert now[k] == r, (name, k, r, now[k])
     added = sorted(set(now) - set(before))
-    assert all("monitor" in k or "K_mon_" in k for k in added), added
+    assert all("monitor" in k or "K_mon_" in k or "K_hist_batch_" in k for k in added), added
