@@ -58,6 +58,11 @@ CASES = {
     "mri_16x32x16": ("mhd_mri_3d", "run.nstepmax=20;run.noutput=5", [0, 5, 20]),
     "mri_16x32x16_s1": ("mhd_mri_3d", "run.nstepmax=1;run.noutput=100", [1]),
     "mri_8x16x8_long": ("mhd_mri_3d", "mesh.nx=8;mesh.ny=16;mesh.nz=8;run.nstepmax=60;run.noutput=1000", [60]),
+    # ... a shear fast enough to pass every row offset and the fmod(., ylen) wrap of the shearing-box remaps (all other MRI cases keep
+    # the shipped omega0 = 1e-3 and never wrap): omega0 = 1 moves the shift ~0.75 cell per step, two wraps of ylen in 14 steps
+    # (tests/shear_phase_checks.py, plant `fast`); omega0 = 0.5 with minmod slopes wraps 12 rows over 40 steps
+    "mri_16x8x8_fastshear": ("mhd_mri_3d", "mesh.nx=16;mesh.ny=8;mesh.nz=8;MHD.omega0=1.0;MRI.amp=0.3;run.nstepmax=14;run.noutput=7", [0, 7, 14]),
+    "mri_8x12x6_fastshear_minmod": ("mhd_mri_3d", "mesh.nx=8;mesh.ny=12;mesh.nz=6;MHD.omega0=0.5;MRI.amp=0.3;hydro.slope_type=1.0;run.nstepmax=40;run.noutput=1000", [40]),
     # --- the other 2D magnetic Riemann solvers (riemann_mhd.h:417-609) and slope_type 3 -----------
     "ot2d_32_hlla": ("orszag-tang", "mesh.nx=32;mesh.ny=32;MHD.magRiemannSolver=hlla;run.nstepmax=20;run.noutput=100", [20]),
     "ot2d_32_hllf": ("orszag-tang", "mesh.nx=32;mesh.ny=32;MHD.magRiemannSolver=hllf;run.nstepmax=20;run.noutput=100", [20]),

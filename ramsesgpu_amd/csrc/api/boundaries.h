@@ -126,7 +126,9 @@ int launch_fill_xy(rgpu_ctx* c, double* U, const FillXY& f, int a1, int b1, int 
   if (n1 + n2 == 0) return 0;
   const unsigned per = 2u * (unsigned)c->g.gw * (unsigned)(c->g.isize + c->g.ny);   // ghost cells of one plane (fill_xy_cell)
   if (stop_now(c)) return 0;
-  K_fill_xy k = {c->g, f, U, per, a1, n1, a2, (f.shear && !RG_SYNC_LAUNCH) ? c->clk_cur : stop_clk(c)};
+  // (shearing box inside a device-clock batch: the offsets at t + dt come from the record -- in the host emulation too, where the
+  // record is already formed, so that the CPU tests run step_clock_form's offsets and not only the host's restatement of them)
+  K_fill_xy k = {c->g, f, U, per, a1, n1, a2, f.shear ? c->clk_cur : stop_clk(c)};
   if (rg_launch<kBlock>(c->stream, per * (unsigned)(n1 + n2), k)) return -1;
   if (c->p.enableJet && !c->g.three_d) return launch_jet(c, U);   // 2D: re-imposed after the Y pass (HydroRunBase.cpp:2286-2312)
   return 0;

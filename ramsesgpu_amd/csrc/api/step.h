@@ -365,7 +365,9 @@ int mhd3d_core(rgpu_ctx* c, const double* in, double* out, double dt_arg, double
     return 0;
   };
   K_shear_save_emf k_ssave = {g, c->emf, c->shear_save};
-  K_shear_remap k_sremap = {g, sr, c->F, c->emf, c->shear_save, c->shear_remap, dtdx, st.clk};
+  // (the host emulation resolves the record by value, st.clk == 0 -- except here: inside a batch the remap takes its offsets from the
+  // record as on the device, so that the CPU tests run step_clock_form's offsets and not only the restatement above)
+  K_shear_remap k_sremap = {g, sr, c->F, c->emf, c->shear_save, c->shear_remap, dtdx, RG_SYNC_LAUNCH ? c->clk_cur : st.clk};
   auto shear_planes = [&](rg_stream_t s, PlaneRange r, PlaneRange r2 = PlaneRange{0, 0}) -> int {  // the two 2D (j,k) kernels restricted to planes r (and r2)
     if (!shear || r.hi <= r.lo) return 0;
     if (use_sweep) {   // the sweep's closing launch saved the emfY columns of its planes: the remap of exactly those

@@ -14,6 +14,13 @@ from ramsesgpu_amd.solver import Solver, interior
 INF = float("inf")
 _REFS = {}
 
+# (base, overrides, steps) run by both test files besides their own lists.  fastshear: the plant `fast` of tests/shear_phase_checks.py --
+# omega0 = 1 moves the shearing-box shift ~0.75 cell per step, every row offset and two wraps of ylen in 14 steps; the samples are taken
+# behind the same clock records the shear remap and the ghost fill read their offsets from
+SHEAR_CASES = [
+    ("mhd_mri_3d", "mesh.nx=16;mesh.ny=8;mesh.nz=8;MHD.omega0=1.0;MRI.amp=0.3", 14),
+]
+
 
 def reference(lib, base, ov, nsteps, keep_all=True):
     """{"dts": dt of step n, "ts": t before step n (n <= nsteps), "rows": history_mri before step n (n <= nsteps), "states": {n: U}}"""

@@ -5,6 +5,8 @@ compares with the oracle (tests/oracle_api.py) or with fixtures produced by the 
 Bar (stated once, used everywhere): BIT-IDENTICAL doubles.  The path is fp64; north_star asks for
 "Orszag-Tang L2 error vs euler_cpu < 1e-12" -- `assert_same` reports that relative L2 too, and fails on the
 stricter bit-identity."""
+import math
+
 import numpy as np
 
 from conftest import golden_cases, ini, load_golden
@@ -123,11 +125,19 @@ def check_boundaries(lib, oracle, base, ov, seed=1):
             sv.upload(U, both=False)
             sv.make_boundaries(0, idim)
             assert_same(sv.getDataHost(0), ref, "%s make_boundaries(dir %d)" % (base, idim))
-        ref = U.copy()
-        oracle.make_all_boundaries(p, ref, 3.7, 0.9)
-        sv.upload(U, both=False)
-        sv.make_all_boundaries(0, 3.7, 0.9)
-        assert_same(sv.getDataHost(0), ref, "%s make_all_boundaries" % base)
+        times = [(3.7, 0.9), (0.0, 0.0)]
+        if p.shearingBoxEnabled and p.Omega0 > 0 and p.three_d:
+            # ... and a (t, dt) whose shift lies in the last row, jplus == ny - 1: half a cell before the wrap of ylen, one wrap behind it
+            rate, ylen = 1.5 * p.Omega0 * (p.dx * p.nx), p.dy * p.ny
+            t_last = (2.0 * ylen - 0.5 * p.dy) / rate
+            assert int(math.fmod(rate * t_last, ylen) / p.dy) == p.ny - 1, (base, ov)
+            times.append((t_last - 0.9, 0.9))
+        for t, dt in times:
+            ref = U.copy()
+            oracle.make_all_boundaries(p, ref, t, dt)
+            sv.upload(U, both=False)
+            sv.make_all_boundaries(0, t, dt)
+            assert_same(sv.getDataHost(0), ref, "%s make_all_boundaries at (t, dt) = (%r, %r)" % (base, t, dt))
     finally:
         sv.close()
 
@@ -623,6 +633,7 @@ BOUNDARY_CASES = [
     ("orszag-tang", "mesh.nx=8;mesh.ny=6"), ("mhd_BrioWu", "mesh.nx=6;mesh.ny=8"), ("jet2d_cpu", "mesh.nx=10;mesh.ny=8;jet.ijet=3;jet.offsetJet=2"),
     ("implode3d", "mesh.nx=6;mesh.ny=5;mesh.nz=4"), ("orszag-tang3d", "mesh.nx=6;mesh.ny=5;mesh.nz=4"),
     ("mhd_mri_3d", "mesh.nx=6;mesh.ny=8;mesh.nz=4;MHD.omega0=0.4"),
+    ("mhd_mri_3d", "mesh.nx=6;mesh.ny=8;mesh.nz=4;MHD.omega0=1.0"),      # fastshear: at (3.7, 0.9) the shift has wrapped ylen
     ("mhd_BrioWu", "mesh.nx=4;mesh.ny=5;mesh.nz=6;mesh.boundary_xmin=1;mesh.boundary_ymax=1;mesh.boundary_zmin=3;mesh.boundary_zmax=3"),
 ]
 

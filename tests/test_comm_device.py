@@ -91,6 +91,8 @@ SMALL = [
     ("orszag-tang3d", "mesh.nx=16;mesh.ny=16;mesh.nz=32;hydro.nu=0.005;MHD.eta=0.01", 3, 2, 1),
     ("orszag-tang3d", "mesh.nx=16;mesh.ny=16;mesh.nz=48;hydro.nu=0.005;MHD.eta=0.01", 3, 3, 1),
     ("mhd_mri_3d", "mesh.nx=16;mesh.ny=24;mesh.nz=40;MRI.amp=0.2;hydro.nu=1.5e-5;MHD.eta=3e-5", 3, 2, 1),   # ... after the shear remap
+    # fastshear: two wraps of ylen in 14 steps, each through a step whose remap / ghost offsets are ny - 1 / 0 (the plant `fast` of tests/shear_phase_checks.py)
+    ("mhd_mri_3d", "mesh.nx=16;mesh.ny=8;mesh.nz=24;MHD.omega0=1.0;MRI.amp=0.3", 14, 2, 1),
 ]
 SCHED = ("serial", "overlap", "boundary-first")
 ENV = {"HSA_ENABLE_IPC_MODE_LEGACY": "0", "COMM_DEVICE": "cuda-staged:0"}
@@ -108,7 +110,7 @@ def test_exact_ranks_in_place_exchange(dev_comm_exact, gpu_lib, oracle, tmp_path
     run_worker("mhd_mri_3d", "mesh.nx=16;mesh.ny=24;mesh.nz=40;" + MRI, 3, 2, 1, tmp_path, env_extra=dict(ENV, COMM_ARITH="exact", RGPU_COMM_PACK="0"), timeout=600)
 
 
-RUN_STEPS = [SMALL[0], SMALL[1], SMALL[3], SMALL[4], SMALL[6], SMALL[7], SMALL[9], SMALL[10], SMALL[13], SMALL[14], SMALL[15], SMALL[16]]
+RUN_STEPS = [SMALL[0], SMALL[1], SMALL[3], SMALL[4], SMALL[6], SMALL[7], SMALL[9], SMALL[10], SMALL[13], SMALL[14], SMALL[15], SMALL[16], SMALL[20]]
 
 
 @pytest.mark.gpu

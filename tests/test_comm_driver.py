@@ -78,6 +78,10 @@ CASES = [
     ("mhd_mri_3d", "mesh.nx=6;mesh.ny=8;mesh.nz=60", 3, 3, 2),
     ("mhd_mri_3d", "mesh.nx=8;mesh.ny=12;mesh.nz=24;MHD.omega0=0.02", 3, 1, 2),       # ring of one
     ("implode3d", "mesh.nx=8;mesh.ny=8;mesh.nz=40", 3, 2, 2),                          # hydro: the sweep is the whole step, same as 1
+    # fastshear (appended: RUN_STEPS indexes by position): omega0 = 1, two wraps of ylen in 14 steps, each through a step whose remap / ghost offsets are ny - 1 / 0 (the plant
+    # `fast` of tests/shear_phase_checks.py) -- the driver forms the offsets per rank, in run_steps from its own clock records
+    ("mhd_mri_3d", "mesh.nx=16;mesh.ny=8;mesh.nz=24;MHD.omega0=1.0;MRI.amp=0.3", 14, 2, 1),
+    ("mhd_mri_3d", "mesh.nx=16;mesh.ny=8;mesh.nz=24;MHD.omega0=1.0;MRI.amp=0.3", 14, 3, 1),
 ]
 
 
@@ -151,7 +155,8 @@ def test_default_schedule_follows_the_slab_thickness(base, ov, nsteps, world, co
 
 RUN_STEPS = [CASES[n] for n in (0, 2, 4, 6, 7, 9, 10, 11, 12, 14, 18, 19, 20, 21, 22, 23)] + [
     ("mhd_mri_3d", "mesh.nx=6;mesh.ny=8;mesh.nz=32;MHD.omega0=0.02", 3, 4, 1),      # four slabs
-    ("mhd_mri_3d", "mesh.nx=6;mesh.ny=8;mesh.nz=64;MHD.omega0=0.02", 3, 4, 2)]
+    ("mhd_mri_3d", "mesh.nx=6;mesh.ny=8;mesh.nz=64;MHD.omega0=0.02", 3, 4, 2),
+    CASES[24], CASES[25]]                                                            # fastshear, 2 and 3 slabs
 
 
 @pytest.mark.parametrize("base,ov,nsteps,world,overlap", RUN_STEPS,

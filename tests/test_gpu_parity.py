@@ -141,6 +141,8 @@ SLAB1 = [
     ("orszag-tang3d", "mesh.nx=24;mesh.ny=24;mesh.nz=40", 4),
     ("orszag-tang3d", "mesh.nx=16;mesh.ny=16;mesh.nz=24;mesh.boundary_xmin=2;mesh.boundary_xmax=2;mesh.boundary_zmin=1;mesh.boundary_zmax=2", 4),
     ("implode3d", "mesh.nx=32;mesh.ny=32;mesh.nz=32;hydro.riemannSolver=hllc", 5),
+    # fastshear: two wraps of ylen in 14 steps, each through a step whose remap / ghost offsets are ny - 1 / 0 (the plant `fast` of tests/shear_phase_checks.py)
+    ("mhd_mri_3d", "mesh.nx=16;mesh.ny=8;mesh.nz=24;MHD.omega0=1.0;MRI.amp=0.3", 14),
 ]
 
 

@@ -52,6 +52,22 @@ def test_device_clock_series_equals_the_lone_context(case, factor, lib):
         sv.close()
 
 
+@pytest.mark.parametrize("base,ov,nsteps", hc.SHEAR_CASES, ids=["fastshear"])
+def test_series_across_the_wrap_of_the_shearing_box(base, ov, nsteps, lib):
+    """the series in one call and in two (the second batch begins after the first wrap of ylen), dtHist = 2.5 x the initial dt; every
+    head after the plain first step queued on the device"""
+    R = hc.reference(lib, base, ov, nsteps)
+    sv = hc.fresh(lib, R)
+    try:
+        S1, V1 = hc.check_series(lib, R, [nsteps], 2.5 * R["dts"][0], sv=sv)
+        if _device_path_expected(lib):
+            assert lib.lib.rgpu_device_time_step_ready(sv.ctx, sv.nStep % 2) == 1 and lib.lib.rgpu_history_batch_heads(sv.ctx) == nsteps - 1
+    finally:
+        sv.close()
+    S2, V2 = hc.check_series(lib, R, [6, nsteps - 6], 2.5 * R["dts"][0])
+    assert len(S1) >= 4 and np.array_equal(S1, S2) and np.array_equal(V1, V2)
+
+
 def test_more_than_one_batch(lib):
     """300 steps in one call (a batch holds 256): tHist and the count cross the batch boundary through the host"""
     R = hc.reference(lib, "orszag-tang", "mesh.nx=48;mesh.ny=40", 300, keep_all=False)

@@ -28,6 +28,15 @@ def test_series_equals_the_lone_context(case, emu_lib):
     assert len(S) >= 3 and S[0] == 0   # the series is not trivially empty: the first turn (tHist == 0) and a few crossings
 
 
+@pytest.mark.parametrize("base,ov,nsteps", hc.SHEAR_CASES, ids=["fastshear"])
+def test_series_across_the_wrap_of_the_shearing_box(base, ov, nsteps, emu_lib):
+    """the series in one call and in two (the second batch begins after the first wrap of ylen), dtHist = 2.5 x the initial dt"""
+    R = hc.reference(emu_lib, base, ov, nsteps)
+    S1, V1 = hc.check_series(emu_lib, R, [nsteps], 2.5 * _dt0(R))
+    S2, V2 = hc.check_series(emu_lib, R, [6, nsteps - 6], 2.5 * _dt0(R))
+    assert len(S1) >= 4 and np.array_equal(S1, S2) and np.array_equal(V1, V2)
+
+
 def test_3d_batches_run_on_the_emulation(emu_lib):
     """the 3D cases above do go through the batch (the emulation's device clock), so the sampling kernels are what was tested"""
     R = hc.reference(emu_lib, MRI[0], MRI[1], NSTEPS)

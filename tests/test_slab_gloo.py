@@ -43,6 +43,10 @@ CASES = [
     ("turbulence_mhd", "mesh.nx=6;mesh.ny=6;mesh.nz=18;hydro.slope_type=2.0", 3, 3, 1),
     ("turbulence_hydro_ou", "mesh.nx=8;mesh.ny=8;mesh.nz=12;turbulence-Ornstein-Uhlenbeck.initialDensityPerturbationAmplitude=0.1", 3, 2, 1),   # Ornstein-Uhlenbeck forcing: same process on every rank
     ("turbulence_mhd_ou", "mesh.nx=6;mesh.ny=6;mesh.nz=18", 3, 3, 1),
+    # fastshear: omega0 = 1 moves the shift ~0.75 cell per step -- two wraps of ylen in 14 steps, each through a step whose remap / ghost offsets are ny - 1 / 0 (the plant `fast` of
+    # tests/shear_phase_checks.py); the offsets are formed per rank, the x ghosts filled plane range by plane range
+    ("mhd_mri_3d", "mesh.nx=16;mesh.ny=8;mesh.nz=24;MHD.omega0=1.0;MRI.amp=0.3", 14, 2, 1),
+    ("mhd_mri_3d", "mesh.nx=16;mesh.ny=8;mesh.nz=24;MHD.omega0=1.0;MRI.amp=0.3", 14, 3, 1),
 ]
 
 
