@@ -519,7 +519,7 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
  * contain it as IEEE addition does; fmin / fmax return their other operand when one is NaN, so the extrema are those of the cells
  * whose term is a number (all terms NaN: +inf / +0.0 stay).  Members do not see each other: a poisoned member changes no other's values.
  *
- *   rgpu_state_monitor     out[RGPU_MON_NQ] of U[parity] of any 2D context, in any configuration (3D: RGPU_EUNSUPPORTED).  Reads the
+ *   rgpu_state_monitor     out[RGPU_MON_NQ] of U[parity] of any 2D context, in any configuration (3D: RGPU_EUNSUPPORTED, see rgpu_state_monitor3d).  Reads the
  *                          state only: ghost cells, CFL slots and what the context knows about them stay as they are.  Synchronises.
  *   rgpu_ensemble_monitor  out[members][RGPU_MON_NQ] of every member's CURRENT state -- U[0] after rgpu_upload, U[nStep % 2] after steps
  *                          taken through rgpu_one_step_integration / rgpu_godunov_unsplit / rgpu_run_steps* on the member or
@@ -543,8 +543,50 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
  *                          sample).  Both give the doubles of rgpu_state_monitor on a lone context holding that state.
  *   rgpu_ensemble_monitor_device_bytes   the extra device memory, allocated by the first call that samples on the device (per member:
  *                          the segment sums, RGPU_CLOCK_BATCH log slots, 8 bytes of bookkeeping; the log as many again in pinned host
- *                          memory).  rgpu_ensemble_device_bytes / _scan_device_bytes do not include it.  0 for refused parameters. */
+ *                          memory).  rgpu_ensemble_device_bytes / _scan_device_bytes do not include it.  0 for refused parameters.
+ *
+ * The 3D monitor: the same ten quantities, names and RGPU_MON_NQ over the nx x ny x nz interior cells of U[parity] as the array stands
+ * (no ghost fill; the high faces of the last interior row, column and plane come from the first ghost layer), raw.  Terms of cell
+ * (i, j, k), IEEE + - * / in this order, no FMA contraction in either library:
+ *     rho, E, mx, my as above, mz = U[IW] (3D hydro has five variables);  ekin = (0.5 * ((mx * mx + my * my) + mz * mz)) / rho
+ *     MHD:   bxc, byc as above, bzc = 0.5 * (Bz(i,j,k) + Bz(i,j,k+1));  emag = 0.5 * ((bxc * bxc + byc * byc) + bzc * bzc)
+ *            absdivb = | ((Bx(i+1,j,k) - Bx(i,j,k)) / dx + (By(i,j+1,k) - By(i,j,k)) / dy) + (Bz(i,j,k+1) - Bz(i,j,k)) / dz |
+ *     hydro: emag = +0.0, absdivb = +0.0;   eint = (E - ekin) - emag
+ * Summation order, fixed by (nx, ny, nz), RGPU_MON_ROWS and RGPU_MON_LANES alone: V[kk], kk = k - ghostWidth, is steps 1 - 4 above
+ * applied to the nx x ny cells of interior plane kk; the result is V[0] + V[1] + .. ascending in kk from +0.0.  The extrema take the
+ * same route with fmin from +inf / fmax from +0.0; the NaN rules are those above.  No floating-point atomics: the values do not depend
+ * on the library, on whether the sample is taken inside or outside a batch, or on how the kernels cut the grid.
+ * (tests/monitor3d_checks.py is this order in numpy.)
+ *
+ *   rgpu_state_monitor3d   out[RGPU_MON_NQ] of U[parity] of any single-domain 3D context, hydro or MHD, rotating and shearing box
+ *                          included.  Reads the state only: ghost cells, CFL slots and what the context knows about them stay as they
+ *                          are.  Synchronises.  2D context: RGPU_EUNSUPPORTED; slab context (slab_count > 1): RGPU_EINVAL, as
+ *                          rgpu_history_mri; NULL pointer: RGPU_EINVAL.
+ *   rgpu_run_steps_monitored   rgpu_run_steps_log (same states, same dt sequence, same return value) of a 2D or 3D context plus sampling,
+ *                          with the semantics of rgpu_ensemble_run_steps_monitored for one member: a sample after each step that brings
+ *                          *nStep to a multiple of `every`; *mon_n = the samples of this call (<= cap = nsteps / every + 1); sample k:
+ *                          mon_step[k], mon_t[k] the host-accumulated *t after that step, mon[k * RGPU_MON_NQ + q] the values of
+ *                          rgpu_state_monitor / rgpu_state_monitor3d on that state, bit for bit.  A step that reaches tEnd is sampled if
+ *                          it qualifies, nothing is sampled after a stop, and after stop code 2 or 3 (a negative return) no further
+ *                          samples are taken; *mon_n counts only samples whose values were written.  A run cut into calls gives the
+ *                          series of one call.  dt_log may be NULL.
+ *                          Where the context takes its time step from the device (rgpu_device_time_step_ready) the monitor kernels are
+ *                          queued behind the last kernel of each qualifying step (3D: csrc/hip/monitor3d.h; 2D: the ensemble's monitor
+ *                          kernels with one member), return in their first instructions when the step's clock record says stop -- the
+ *                          host knows the step number, only "did the step run" comes from the record, which on small 2D hydro grids is
+ *                          written by that step's own kernel -- and write to a device log of RGPU_CLOCK_BATCH slots that is copied back
+ *                          once per batch with the clock records: no synchronisation inside a batch.  Everywhere else (first steps,
+ *                          gravity, the dissipative stage, forcing, a rotating 2D box, phase timers, option "step_clock" = 0) the call
+ *                          is the literal loop: rgpu_one_step_integration, then rgpu_state_monitor / rgpu_state_monitor3d.
+ *                          Partial sums go to the flux array, dead between steps; the log (RGPU_CLOCK_BATCH x RGPU_MON_NQ doubles + 8
+ *                          bytes) and its pinned mirror are allocated by the first call that needs them, freed with the context, and
+ *                          are not part of rgpu_device_bytes.
+ *                          Errors: RGPU_EINVAL for every < 1 ("every" in the message), a NULL pointer among nStep, t, dt, mon_n,
+ *                          mon_step, mon_t, mon, nsteps < 0, or a slab context.
+ *   rgpu_monitor_batch_samples   how many samples this context has queued on the device inside its batches so far (0 where every call
+ *                          took the literal loop): lets a caller (and the tests) tell which path ran, as rgpu_history_batch_heads. */
 #define RGPU_MON_NQ 10
+#define RGPU_MON_NAMES "mass mx my mz E ekin emag min_rho min_eint max_absdivb"   /* the RGPU_MON_NQ columns, in order */
 #define RGPU_MON_ROWS 32    /* rows per segment of the summation order */
 #define RGPU_MON_LANES 64   /* lanes of the summation order (one wavefront) */
 int rgpu_state_monitor(rgpu_ctx* c, int parity, double* out /* [RGPU_MON_NQ] */);
@@ -554,6 +596,10 @@ int rgpu_ensemble_run_steps_monitored(rgpu_ensemble* e, int nsteps, const double
                                       int every, int* mon_n /* [members] */, int* mon_step /* [members][cap] */,
                                       double* mon_t /* [members][cap] */, double* mon /* [members][cap][RGPU_MON_NQ] */);
 size_t rgpu_ensemble_monitor_device_bytes(const rgpu_params* p, int members);
+int rgpu_state_monitor3d(rgpu_ctx* c, int parity, double* out /* [RGPU_MON_NQ] */);
+int rgpu_run_steps_monitored(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log,
+                             int every, int* mon_n, int* mon_step /* [cap] */, double* mon_t /* [cap] */, double* mon /* [cap][RGPU_MON_NQ] */);
+long rgpu_monitor_batch_samples(rgpu_ctx* c);
 
 /* Self-test of the device arithmetic the parity contract rests on: for n operand pairs computes on the device
  *   quot[i]  = rg_div(num[i], rg_recip(den[i]))   the shared-reciprocal division of csrc/hip/rg_backend.h

@@ -211,6 +211,14 @@ def declare_device_api(lib):
     lib.rgpu_clock_check.argtypes = [ctx]
     lib.rgpu_state_monitor.restype = C.c_int
     lib.rgpu_state_monitor.argtypes = [ctx, C.c_int, c_double_p]
+    if hasattr(lib, "rgpu_state_monitor3d"):   # (absent from an older build of the library: scripts/monitor_bench.py --baseline-lib)
+        lib.rgpu_state_monitor3d.restype = C.c_int
+        lib.rgpu_state_monitor3d.argtypes = [ctx, C.c_int, c_double_p]
+        lib.rgpu_run_steps_monitored.restype = C.c_int
+        lib.rgpu_run_steps_monitored.argtypes = [ctx, C.c_int, C.c_double, C.POINTER(C.c_int), c_double_p, c_double_p, c_double_p, C.c_int,
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]
+        lib.rgpu_monitor_batch_samples.restype = C.c_long
+        lib.rgpu_monitor_batch_samples.argtypes = [ctx]
     return lib
 
 
@@ -260,4 +268,5 @@ DECLARED_SYMBOLS = [
     "rgpu_ensemble_create", "rgpu_ensemble_destroy", "rgpu_ensemble_members", "rgpu_ensemble_member", "rgpu_ensemble_device_bytes", "rgpu_ensemble_last_error", "rgpu_ensemble_run_steps",
     "rgpu_ensemble_create_scan", "rgpu_ensemble_scan_device_bytes",
     "rgpu_state_monitor", "rgpu_ensemble_monitor", "rgpu_ensemble_run_steps_monitored", "rgpu_ensemble_monitor_device_bytes",
+    "rgpu_state_monitor3d", "rgpu_run_steps_monitored", "rgpu_monitor_batch_samples",
 ]

@@ -73,6 +73,11 @@ struct rgpu_ctx {
   // in pinned host memory, allocated by the first call that needs them
   HistBatchRec* d_hist; HistBatchRec* h_hist;
   long hist_heads;              // history heads queued on the device so far (rgpu_history_batch_heads: lets a caller tell which path ran)
+  // the monitor samples taken inside a batch (kernels_monitor.h; rgpu_run_steps_monitored): kClockBatch slots of MON_NQ doubles on the
+  // device (+ one zeroed double: the bookkeeping the ensemble's monitor kernels read for a lone 2D context) / in pinned host memory,
+  // allocated by the first call that needs them
+  double* d_mon; double* h_mon;
+  long mon_samples;             // monitor samples queued on the device so far (rgpu_monitor_batch_samples)
   // fused 2D steps: the clock is folded into the step kernel itself (step_clock_rec.h: ClockFold) over three rotating slot arrays;
   // d_red always points at the array that holds the maxima of the current state
   unsigned long long* d_red_base;   // 3 x RG_DT_SLOTS
@@ -261,7 +266,7 @@ int create_common(const rgpu_params* p, double* dU, double* dU2, void* hip_strea
   c->G = 0;
   c->Frc = 0;
   c->ou = 0;
-  c->d_red = 0; c->d_red_base = 0; c->fold_mode = false; c->fold_request = false; c->fold_pending = false; c->fold_phase0 = 0; c->h_red = 0; c->d_clk = 0; c->h_clk = 0; c->d_hist = 0; c->h_hist = 0; c->hist_heads = 0; c->clk_cur = 0; c->clk_n = -1; c->clk_t0 = 0.0; c->clk_tEnd = 0.0;
+  c->d_red = 0; c->d_red_base = 0; c->fold_mode = false; c->fold_request = false; c->fold_pending = false; c->fold_phase0 = 0; c->h_red = 0; c->d_clk = 0; c->h_clk = 0; c->d_hist = 0; c->h_hist = 0; c->hist_heads = 0; c->d_mon = 0; c->h_mon = 0; c->mon_samples = 0; c->clk_cur = 0; c->clk_n = -1; c->clk_t0 = 0.0; c->clk_tEnd = 0.0;
   c->scratch_bytes = 0;
   c->timers_on = false; c->ev_ok = false;
   for (int i = 0; i < RGPU_T_COUNT; ++i) { c->t_acc[i] = 0; c->t_calls[i] = 0; }

@@ -145,16 +145,22 @@ struct HistRun {
 };
 static_assert((int)HIST_BATCH_NQ == RGPU_HIST_NQ, "include/rgpu.h states the width of a history row");
 
+// what rgpu_run_steps_monitored adds to the loop: the cadence in steps and where the samples go (see include/rgpu.h)
+struct MonRun {
+  int every;
+  int* n; int* step; double* t; double* v;   // *n samples so far; step[k], t[k], v[k][RGPU_MON_NQ]
+};
+
 // rgpu_run_steps_log; *why = 0, or the stop code of the record that ended the run (1: tEnd, 2: dt is not a number, 3: 1/dt is not
-// finite -- the last two are also reported as RGPU_EHIP).  H != 0: rgpu_run_steps_history
-static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int* why, const HistRun* H = 0) {
+// finite -- the last two are also reported as RGPU_EHIP).  H != 0: rgpu_run_steps_history.  M != 0: rgpu_run_steps_monitored
+static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int* why, const HistRun* H = 0, const MonRun* M = 0) {
   *why = 0;
   int done = 0;
   struct Current { rgpu_ctx* c; const int* n; ~Current() { c->cur = *n & 1; } } current = {c, nStep};   // however the loop is left: U[*nStep % 2] is the state
   (void)current;
   while (done < nsteps && *t < tEnd) {
     const int parity = *nStep % 2;
-    if (!clock_ready(c, parity) || (H && !H->batch)) {   // the reference's loop body (the first step of a run always comes through here)
+    if (!clock_ready(c, parity) || (H && !H->batch) || (M && !monitor_batch_ok(c))) {   // the reference's loop body (the first step of a run always comes through here)
       if (H && hist_batch_due(*t, *dt, *H->tHist, H->dtHist)) {   // ... with the head of MHDRunGodunov.cpp:3975-3984, literally
         const int k = *H->n;
         if (const int rch = rgpu_history_mri(c, parity, H->v + (size_t)k * RGPU_HIST_NQ)) return rch;
@@ -166,8 +172,16 @@ static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, doub
       if (rc) return rc;
       if (dt_log) dt_log[done] = *dt;
       ++done;
+      if (M && *nStep % M->every == 0) {   // the state the step left, U[*nStep % 2]: one synchronisation per sample on this path
+        const int k = *M->n;
+        double* v = M->v + (size_t)k * RGPU_MON_NQ;
+        if (const int rcm = c->g.three_d ? rgpu_state_monitor3d(c, *nStep & 1, v) : rgpu_state_monitor(c, *nStep & 1, v)) return rcm;
+        M->step[k] = *nStep; M->t[k] = *t;
+        *M->n = k + 1;
+      }
       continue;
     }
+    if (M && monitor_batch_alloc(c)) return RG_HIPFAIL(c, "run_steps_monitored: log of the batch");
     const int m = (nsteps - done < rgpu_ctx::kClockBatch) ? nsteps - done : (int)rgpu_ctx::kClockBatch;
     if (H && !c->d_hist) {    // the log of a batch and its pinned mirror: allocated by the first call that needs them
       if (rg_malloc((void**)&c->d_hist, rgpu_ctx::kClockBatch * sizeof(HistBatchRec)) || rg_host_alloc((void**)&c->h_hist, rgpu_ctx::kClockBatch * sizeof(HistBatchRec))) {
@@ -193,6 +207,8 @@ static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, doub
       if (rc == 0 && H && history_batch_queue(c, n, queued, dt0, *H->tHist, H->dtHist)) rc = RGPU_EHIP;
       if (rc == 0) rc = (step_pre(c, n) || step_core(c, n, 0.0, 0.0) || step_post_a(c, n, 0.0, 0.0) || step_post_b(c, n)) ? RGPU_EHIP : 0;
       if (rc == 0 && !c->rec.slots((n + 1) % 2)) rc = RGPU_EHIP;   // (cannot happen: same configuration, same kernels)
+      // the tail of the turn: the monitor of U[(n + 1) % 2] behind the step's last kernel, taken if the record says that the step ran
+      if (rc == 0 && M && (n + 1) % M->every == 0 && monitor_batch_queue(c, (n + 1) & 1, queued)) rc = RGPU_EHIP;
       if (rc) { c->clk_n = queued; break; }   // the record of the step that failed to queue is not read back
     }
     // a launch that failed after `queued` complete steps were queued: those steps still run on the device -- read their records and
@@ -202,10 +218,25 @@ static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, doub
     // the log travels with the clock records: queued behind them here, complete after the one synchronisation of rgpu_clock_close
     const int nlog = H ? queued : 0;   // (a record behind the last head queued is copied unwritten and not read)
     const bool log_ok = nlog == 0 || rg_copy_d2h(c->h_hist, c->d_hist, (size_t)nlog * sizeof(HistBatchRec), c->stream) == 0;
+    // ... and so do the monitor slots (a slot no sample was queued for, or whose step did not run, is copied unwritten and not read)
+    const bool mon_ok = !M || queued == 0 || rg_copy_d2h(c->h_mon, c->d_mon, (size_t)queued * RGPU_MON_NQ * sizeof(double), c->stream) == 0;
+    const double t_open = *t;
     const int rc2 = rgpu_clock_close(c, n0, &ran, t, dt, dt_log ? dt_log + done : 0, &stop);
     if (rc2) return rc2;
     *nStep += ran;
     done += ran;
+    if (M && ran > 0) {   // the host knows the step numbers; that step n0 + r ran is what the records said
+      if (!mon_ok) { c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps_monitored: read-back of the log"); }
+      double ta = t_open;
+      for (int r = 0; r < ran; ++r) {
+        ta += c->h_clk[r].dt;   // (*t as rgpu_clock_close accumulated it)
+        if ((n0 + r + 1) % M->every) continue;
+        const int k = *M->n;
+        M->step[k] = n0 + r + 1; M->t[k] = ta;
+        for (int q = 0; q < RGPU_MON_NQ; ++q) M->v[(size_t)k * RGPU_MON_NQ + q] = c->h_mon[(size_t)r * RGPU_MON_NQ + q];
+        *M->n = k + 1;
+      }
+    }
     if (H && ran > 0) {   // a step that ran had its head queued in front of it: records [0, ran) are written (ran <= nlog)
       if (!log_ok || ran > nlog) { c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps_history: read-back of the log"); }
       for (int r = 0; r < ran; ++r) {
@@ -253,6 +284,22 @@ int rgpu_run_steps_history(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, dou
   const HistRun H = {dtHist, tHist, hist_n, hist_step, hist_t, hist_dt, hist, rgpu::options().history_batch != 0};
   int why = 0;
   return run_steps_impl(c, nsteps, tEnd, nStep, t, dt, dt_log, &why, &H);
+}
+
+long rgpu_monitor_batch_samples(rgpu_ctx* c) { return c ? c->mon_samples : 0; }
+
+int rgpu_run_steps_monitored(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int every,
+                             int* mon_n, int* mon_step, double* mon_t, double* mon) {
+  RG_CHECK_CTX(c);
+  if (!nStep || !t || !dt || !mon_n || !mon_step || !mon_t || !mon) return fail(c, RGPU_EINVAL, "run_steps_monitored: null pointer");
+  *mon_n = 0;
+  if (!c->U[0]) return fail(c, RGPU_EINVAL, "run_steps_monitored: context without state");
+  if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, "run_steps_monitored: single-domain contexts only (a slab holds a part of the box)");
+  if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_monitored: nsteps is negative");
+  if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_monitored: every must be at least 1");
+  const MonRun M = {every, mon_n, mon_step, mon_t, mon};
+  int why = 0;
+  return run_steps_impl(c, nsteps, tEnd, nStep, t, dt, dt_log, &why, 0, &M);
 }
 
 }  // extern "C"

@@ -710,6 +710,42 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
   const bool history_batched = history_kind != 0 && p_.nz_global != 1 && (long long)p_.nx * p_.ny * p_.nz <= kHistoryBatchMaxCells;
   std::vector<int> hist_step;
   std::vector<double> hist_t, hist_dt, hist_v;
+  // [monitor] enabled=yes: <outputDir>/<outputPrefix>_<filename> gets the ten doubles of rgpu_state_monitor / rgpu_state_monitor3d
+  // (include/rgpu.h, "monitors") after every step that brings nStep to a multiple of `every`, hydro and MHD, 2D and 3D, with 17
+  // significant digits (the doubles round-trip).  The quiet turns go through rgpu_run_steps_monitored (the samples taken on the device
+  // inside the device-clock batches); with a history file as well the loop keeps its history handling, is cut at the sampling steps
+  // and takes the rows by the direct calls -- the same doubles either way.  Not for z-slab runs (a slab holds a part of the box).
+  const bool monitorEnabled = cfg_.get_bool("monitor", "enabled", false);
+  const int mon_every = monitorEnabled ? (int)cfg_.get_integer("monitor", "every", 10) : 0;
+  if (monitorEnabled && mon_every < 1) throw std::runtime_error("[monitor] every must be at least 1");
+  bool noted_mon = false;
+  if (monitorEnabled && (slab() || hooked_)) note_once(&noted_mon, "z-slab run: the monitor file is not written");
+  const bool monitor_on = monitorEnabled && !slab() && !hooked_;
+  const std::string mon_path = monitor_on ? rs_.outputDir + "/" + rs_.outputPrefix + "_" + cfg_.get_string("monitor", "filename", "monitor.txt") : std::string();
+  const auto monitor_rows = [&](int n, const int* step, const double* t, const double* v) {
+    std::ofstream f(mon_path.c_str(), std::ios::app);
+    if (!f) throw std::runtime_error("cannot write " + mon_path);
+    char num[40];
+    for (int k = 0; k < n; ++k) {
+      f << step[k];
+      std::snprintf(num, sizeof(num), " %.17g", t[k]);
+      f << num;
+      for (int q = 0; q < RGPU_MON_NQ; ++q) { std::snprintf(num, sizeof(num), " %.17g", v[(size_t)k * RGPU_MON_NQ + q]); f << num; }
+      f << "\n";
+    }
+  };
+  const auto monitor_direct = [&](int n) {   // the row of the current state U[n % 2]
+    double v[RGPU_MON_NQ];
+    check(p_.nz_global != 1 ? rgpu_state_monitor3d(ctx_, n % 2, v) : rgpu_state_monitor(ctx_, n % 2, v), "state_monitor");
+    monitor_rows(1, &n, &totalTime_, v);
+  };
+  if (monitor_on && !(totalTime_ > 0)) {   // the start of a run
+    std::ofstream f(mon_path.c_str(), std::ios::trunc);
+    if (!f) throw std::runtime_error("cannot write " + mon_path);
+    f << "# nStep totalTime " RGPU_MON_NAMES "\n";
+  }
+  std::vector<int> mon_step;
+  std::vector<double> mon_t, mon_v;
   const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   while (totalTime_ < rs_.tEnd && nStep < rs_.nStepmax) {
     if (rs_.nLog > 0 && (nStep % rs_.nLog) == 0 && p_.slab_rank == 0)
@@ -740,7 +776,17 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
       if (rs_.nLog > 0 && rs_.nLog - nStep % rs_.nLog < quiet) quiet = rs_.nLog - nStep % rs_.nLog;
       if (rs_.nOutput > 0 && rs_.nOutput - nStep % rs_.nOutput < quiet) quiet = rs_.nOutput - nStep % rs_.nOutput;
     }
-    if (history_batched) {
+    const bool monitor_batched = monitor_on && !historyEnabled && quiet > 1;
+    if (monitor_on && !monitor_batched && mon_every - nStep % mon_every < quiet) quiet = mon_every - nStep % mon_every;   // the direct call follows
+    const int nStep_before = nStep;
+    if (monitor_batched) {
+      int mn = 0;
+      const size_t cap = (size_t)(quiet / mon_every + 1);
+      if (mon_step.size() < cap) { mon_step.resize(cap); mon_t.resize(cap); mon_v.resize(cap * RGPU_MON_NQ); }
+      const int rc = rgpu_run_steps_monitored(ctx_, quiet, rs_.tEnd, &nStep, &totalTime_, &dt, 0, mon_every, &mn, mon_step.data(), mon_t.data(), mon_v.data());
+      monitor_rows(mn, mon_step.data(), mon_t.data(), mon_v.data());
+      if (rc < 0) check(rc, "run_steps_monitored");
+    } else if (history_batched) {
       int hn = 0;
       if ((int)hist_step.size() < quiet) { hist_step.resize(quiet); hist_t.resize(quiet); hist_dt.resize(quiet); hist_v.resize((size_t)quiet * RGPU_HIST_NQ); }
       const int rc = rgpu_run_steps_history(ctx_, quiet, rs_.tEnd, &nStep, &totalTime_, &dt, 0, dtHist, &tHist, &hn, hist_step.data(), hist_t.data(), hist_dt.data(), hist_v.data());
@@ -757,6 +803,7 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     } else {
       oneStepIntegration(nStep, totalTime_, dt);
     }
+    if (monitor_on && !monitor_batched && nStep > nStep_before && nStep % mon_every == 0) monitor_direct(nStep);
   }
   check(rgpu_synchronize(ctx_), "synchronize");
   if (hooked_) hook_check(hooks_.barrier(hooks_.self), "barrier");

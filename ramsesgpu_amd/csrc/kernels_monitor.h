@@ -31,6 +31,7 @@
 // return their other operand when one is NaN, so a NaN cell drops out of the extrema (it propagates into the sums).
 #pragma once
 #include "dev_numerics.h"
+#include "step_clock_rec.h"
 
 namespace rgpu_dev {
 
@@ -160,6 +161,125 @@ struct K_mon_lanes {
     mon_lane(g.nx, mon_nseg(g.ny), part, (int)l, a);
 #pragma unroll
     for (int q = 0; q < MON_NQ; ++q) lanes[l * MON_NQ + q] = a[q];
+  }
+};
+
+// ---- the monitor of a 3D state (rgpu_state_monitor3d, rgpu_run_steps_monitored) ------------------------------------------------
+// The same ten quantities over the nx x ny x nz interior cells.  Terms of cell (i, j, k), o its flat index:
+//   rho, E, mx, my as above, mz = U[IW] (3D hydro has five variables), ekin as above
+//   MHD:   bxc, byc as above, bzc = 0.5 * (Bz(i,j,k) + Bz(i,j,k+1)), emag = 0.5 * ((bxc * bxc + byc * byc) + bzc * bzc)
+//          divb = | ((Bx(i+1,j,k) - Bx(i,j,k)) / dx + (By(i,j+1,k) - By(i,j,k)) / dy) + (Bz(i,j,k+1) - Bz(i,j,k)) / dz |
+//   hydro: emag = +0.0, divb = +0.0;   eint = (E - ekin) - emag
+// The high faces of the last interior row / column / plane come from the first ghost layer (hist_row_cell reads the same faces).
+// Summation order: V[kk], kk = k - gw, is steps 1 - 4 above applied to the nx x ny cells of interior plane kk; the result is
+// V[0] + V[1] + .. ascending in kk from +0.0 (fmin from +inf / fmax from +0.0 for the extrema).
+RG_DEVFN void mon_vol_cell_terms(const DevParams& g, const double* __restrict__ U, unsigned o, double* t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const size_t N = g.ncell;
+  const double rho = U[o + ID * N], E = U[o + IP * N], mx = U[o + IU * N], my = U[o + IV * N], mz = U[o + IW * N];
+  const double ekin = (0.5 * ((mon_mul(mx, mx) + mon_mul(my, my)) + mon_mul(mz, mz))) / rho;
+  double emag = 0.0, divb = 0.0;
+  if (g.mhd) {
+    const double bx = U[o + IA * N], bx1 = U[o + 1 + IA * N], by = U[o + IB * N], by1 = U[o + g.sj + IB * N];
+    const double bz = U[o + IC * N], bz1 = U[o + g.sk + IC * N];
+    const double bxc = 0.5 * (bx + bx1), byc = 0.5 * (by + by1), bzc = 0.5 * (bz + bz1);
+    emag = mon_mul(0.5, (mon_mul(bxc, bxc) + mon_mul(byc, byc)) + mon_mul(bzc, bzc));
+    divb = fabs(((bx1 - bx) / g.dx + (by1 - by) / g.dy) + (bz1 - bz) / g.dz);
+  }
+  t[0] = rho; t[1] = mx; t[2] = my; t[3] = mz; t[4] = E; t[5] = ekin; t[6] = emag;
+  t[7] = rho; t[8] = (E - ekin) - emag; t[9] = divb;
+}
+
+// step 1 of interior plane kk: P[s][ii]
+RG_DEVFN void mon_vol_segment(const DevParams& g, const double* __restrict__ U, int kk, int s, int ii, double* a) {
+  mon_init(a);
+  const int j0 = s * MON_ROWS, j1 = j0 + MON_ROWS < g.ny ? j0 + MON_ROWS : g.ny;
+  const unsigned o0 = (unsigned)(ii + g.gw) + g.sk * (unsigned)(kk + g.gw);
+  for (int jj = j0; jj < j1; ++jj) {
+    double t[MON_NQ];
+    mon_vol_cell_terms(g, U, o0 + g.sj * (unsigned)(jj + g.gw), t);
+    mon_combine(a, t);
+  }
+}
+// steps 1 and 2 of interior plane kk by one thread: C[ii], an accumulator per segment, the segments added in ascending order -- the
+// additions of mon_lane's inner loop over P[s][ii], hence its bits
+RG_DEVFN void mon_vol_column(const DevParams& g, const double* __restrict__ U, int kk, int ii, double* c) {
+  mon_init(c);
+  const int nseg = mon_nseg(g.ny);
+  for (int s = 0; s < nseg; ++s) {
+    double a[MON_NQ];
+    mon_vol_segment(g, U, kk, s, ii, a);
+    mon_combine(c, a);
+  }
+}
+// one quantity of mon_combine
+RG_MON_FN double mon_op(int q, double a, double x) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return q < MON_NSUM ? a + x : (q < 9 ? fmin(a, x) : fmax(a, x));
+}
+// the sum over the planes: quantity q of V[kk] at V[kk * stride + q], ascending in kk
+RG_DEVFN double mon_vol_planes(int nz, const double* __restrict__ V, size_t stride, int q) {
+  double a = q < MON_NSUM ? 0.0 : (q < 9 ? __builtin_huge_val() : 0.0);
+  for (int kk = 0; kk < nz; ++kk) a = mon_op(q, a, V[(size_t)kk * stride + q]);
+  return a;
+}
+
+// A sample taken inside a batch of device-clock steps (rgpu_run_steps_monitored): every kernel of it is queued behind the last
+// kernel of the step and returns at once when the step's record says that the step did not run (clk == 0: outside a batch)
+RG_DEVFN bool mon_gate_open(const StepClock* clk) { return !clk || clk->stop == 0; }
+
+// ---- the flat kernels of the 3D monitor (rg_launch): the host emulation and any backend without kernels of its own ----------------
+// Scratch: cols[kk][q][ii] (mon_lane's layout of one segment per plane), then two arrays of lane values [kk][l][q] the butterfly
+// alternates between (one launch per stage: "for all l at once").
+// thread idx = kk * nx + ii (coalesced in ii)
+struct K_mon_vol_cols {
+  DevParams g; const double* U; double* cols; const StepClock* clk;
+  RG_DEVFN void operator()(unsigned idx) const {
+    if (!mon_gate_open(clk)) return;
+    const int kk = (int)(idx / (unsigned)g.nx), ii = (int)(idx % (unsigned)g.nx);
+    if (kk >= g.nz) return;
+    double c[MON_NQ];
+    mon_vol_column(g, U, kk, ii, c);
+#pragma unroll
+    for (int q = 0; q < MON_NQ; ++q) cols[((size_t)kk * MON_NQ + q) * g.nx + ii] = c[q];
+  }
+};
+// thread idx = kk * MON_LANES + l (a lane without a column: the neutral elements)
+struct K_mon_vol_lanes {
+  DevParams g; const double* cols; double* lanes; const StepClock* clk;
+  RG_DEVFN void operator()(unsigned idx) const {
+    if (!mon_gate_open(clk)) return;
+    const int kk = (int)(idx / (unsigned)MON_LANES), l = (int)(idx % (unsigned)MON_LANES);
+    if (kk >= g.nz) return;
+    double a[MON_NQ];
+    mon_lane(g.nx, 1, cols + (size_t)kk * MON_NQ * g.nx, l, a);
+#pragma unroll
+    for (int q = 0; q < MON_NQ; ++q) lanes[(size_t)idx * MON_NQ + q] = a[q];
+  }
+};
+// one stage of the butterfly of every plane: dst[l] = src[l] (+) src[l ^ off]
+struct K_mon_vol_fly {
+  int nz, off; const double* src; double* dst; const StepClock* clk;
+  RG_DEVFN void operator()(unsigned idx) const {
+    if (!mon_gate_open(clk) || idx >= (unsigned)nz * MON_LANES) return;
+    double a[MON_NQ];
+#pragma unroll
+    for (int q = 0; q < MON_NQ; ++q) a[q] = src[(size_t)idx * MON_NQ + q];
+    mon_combine(a, src + (size_t)(idx ^ (unsigned)off) * MON_NQ);
+#pragma unroll
+    for (int q = 0; q < MON_NQ; ++q) dst[(size_t)idx * MON_NQ + q] = a[q];
+  }
+};
+// thread q: out[q] = V[0][q] + V[1][q] + ..; V[kk] is lane 0 of plane kk
+struct K_mon_vol_finish {
+  int nz; const double* lanes; double* out; const StepClock* clk;
+  RG_DEVFN void operator()(unsigned q) const {
+    if (!mon_gate_open(clk) || q >= (unsigned)MON_NQ) return;
+    out[q] = mon_vol_planes(nz, lanes, (size_t)MON_LANES * MON_NQ, (int)q);
   }
 };
 

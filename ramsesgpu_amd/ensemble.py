@@ -2,17 +2,12 @@
 its own state, dt sequence and end time, advanced by one step-kernel launch and one clock-kernel launch per step for all of them.
 `Ensemble(p, M)`: M boxes of one parameter set; `Ensemble.scan([p_0, ..])`: a parameter scan, one set per member.
 No numerics live here: `Ensemble` owns the C object, `member(m)` is a `Solver` view of one member's borrowed context."""
-import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _capi
-from .solver import RgpuError, Solver, load_library
-
-
-# the series of one member out of run_steps_monitored: step numbers [n], times [n], values [n, 10] (columns _capi.MON_NAMES)
-MonitorSeries = collections.namedtuple("MonitorSeries", "step t values")
+from .solver import MonitorSeries, RgpuError, Solver, load_library   # (MonitorSeries: the series of one member out of run_steps_monitored)
 
 
 class _Member(Solver):

@@ -5,6 +5,7 @@
 oneStepIntegration, copyGpuToCpu / getDataHost.  No numerics live here: every call goes to librgpu.so, which
 fails loudly (RGPU_ENODEVICE) when there is no GPU.
 """
+import collections
 import ctypes as C
 import os
 
@@ -14,6 +15,10 @@ from . import _capi
 from ._capi import RgpuParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+
+# the series out of run_steps_monitored (of a Solver, of one member of an Ensemble): step numbers [n], times [n], values [n, 10]
+# (columns _capi.MON_NAMES)
+MonitorSeries = collections.namedtuple("MonitorSeries", "step t values")
 
 
 def lib_path(arithmetic=None):
@@ -252,11 +257,31 @@ class Solver:
 
     def state_monitor(self, parity=None):
         """the ten monitor quantities of U[parity] (default: nStep % 2), columns _capi.MON_NAMES: totals of mass, momenta and energies,
-        min density, min internal energy, max |div B| over the interior of a 2D state, raw (rgpu_state_monitor, include/rgpu.h)"""
+        min density, min internal energy, max |div B| over the interior of the state, raw (2D: rgpu_state_monitor, 3D:
+        rgpu_state_monitor3d; include/rgpu.h)"""
         out = np.zeros(_capi.MON_NQ)
         par = self.nStep % 2 if parity is None else int(parity)
-        self._chk(self.lib.rgpu_state_monitor(self.ctx, par, out.ctypes.data_as(_capi.c_double_p)), "state_monitor")
+        fn = self.lib.rgpu_state_monitor3d if self.p.nz_global != 1 else self.lib.rgpu_state_monitor
+        self._chk(fn(self.ctx, par, out.ctypes.data_as(_capi.c_double_p)), "state_monitor")
         return out
+
+    def run_steps_monitored(self, nsteps, every, tEnd=float("inf")):
+        """run_steps with a monitor sample after every step that brings nStep to a multiple of `every` (rgpu_run_steps_monitored: inside
+        the device-clock batches the samples are taken on the device, one read-back per batch).  Returns (done, MonitorSeries): the
+        steps done and the samples of this call -- .step [n], .t [n] (the time after that step), .values [n, 10] (_capi.MON_NAMES)"""
+        cap = max(int(nsteps), 0) // max(int(every), 1) + 1
+        n, t, d, mn = C.c_int(self.nStep), C.c_double(self.totalTime), C.c_double(self.dt), C.c_int(0)
+        log = (C.c_double * max(int(nsteps), 1))()
+        mstep, mt, mv = np.zeros(cap, dtype=np.intc), np.zeros(cap), np.zeros((cap, _capi.MON_NQ))
+        done = self.lib.rgpu_run_steps_monitored(self.ctx, int(nsteps), float(tEnd), C.byref(n), C.byref(t), C.byref(d), log, int(every), C.byref(mn),
+                                                 mstep.ctypes.data_as(C.POINTER(C.c_int)), mt.ctypes.data_as(_capi.c_double_p), mv.ctypes.data_as(_capi.c_double_p))
+        k = mn.value
+        self.nStep, self.totalTime, self.dt = n.value, t.value, d.value   # (they describe the steps that ran, also when the call failed)
+        self.monitor_series = MonitorSeries(mstep[:k].astype(int), mt[:k].copy(), mv[:k].copy())
+        if done < 0:
+            self._chk(done, "run_steps_monitored")
+        self.dt_log = [log[i] for i in range(done)]
+        return done, self.monitor_series
 
     def history_turbulence(self, nStep=None):
         """history_turbulence (MHDRunBase.cpp:3626-3810) reduced on the device: the 18 columns after totalTime and dt"""
