@@ -571,15 +571,15 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
  *                          samples are taken; *mon_n counts only samples whose values were written.  A run cut into calls gives the
  *                          series of one call.  dt_log may be NULL.
  *                          Where the context takes its time step from the device (rgpu_device_time_step_ready) the monitor kernels are
- *                          queued behind the last kernel of each qualifying step (3D: csrc/hip/monitor3d.h; 2D: the ensemble's monitor
- *                          kernels with one member), return in their first instructions when the step's clock record says stop -- the
+ *                          queued behind the last kernel of each qualifying step (csrc/hip/monitor3d.h; a 2D state is a volume of one
+ *                          plane, whose sum over the planes is left out), return in their first instructions when the step's clock record says stop -- the
  *                          host knows the step number, only "did the step run" comes from the record, which on small 2D hydro grids is
  *                          written by that step's own kernel -- and write to a device log of RGPU_CLOCK_BATCH slots that is copied back
  *                          once per batch with the clock records: no synchronisation inside a batch.  Everywhere else (first steps,
  *                          gravity, the dissipative stage, forcing, a rotating 2D box, phase timers, option "step_clock" = 0) the call
  *                          is the literal loop: rgpu_one_step_integration, then rgpu_state_monitor / rgpu_state_monitor3d.
- *                          Partial sums go to the flux array, dead between steps; the log (RGPU_CLOCK_BATCH x RGPU_MON_NQ doubles + 8
- *                          bytes) and its pinned mirror are allocated by the first call that needs them, freed with the context, and
+ *                          Partial sums go to the flux array, dead between steps; the log (RGPU_CLOCK_BATCH x RGPU_MON_NQ doubles)
+ *                          and its pinned mirror are allocated by the first call that needs them, freed with the context, and
  *                          are not part of rgpu_device_bytes.
  *                          Errors: RGPU_EINVAL for every < 1 ("every" in the message), a NULL pointer among nStep, t, dt, mon_n,
  *                          mon_step, mon_t, mon, nsteps < 0, or a slab context.

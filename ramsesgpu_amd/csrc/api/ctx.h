@@ -74,8 +74,7 @@ struct rgpu_ctx {
   HistBatchRec* d_hist; HistBatchRec* h_hist;
   long hist_heads;              // history heads queued on the device so far (rgpu_history_batch_heads: lets a caller tell which path ran)
   // the monitor samples taken inside a batch (kernels_monitor.h; rgpu_run_steps_monitored): kClockBatch slots of MON_NQ doubles on the
-  // device (+ one zeroed double: the bookkeeping the ensemble's monitor kernels read for a lone 2D context) / in pinned host memory,
-  // allocated by the first call that needs them
+  // device / in pinned host memory, allocated by the first call that needs them
   double* d_mon; double* h_mon;
   long mon_samples;             // monitor samples queued on the device so far (rgpu_monitor_batch_samples)
   // fused 2D steps: the clock is folded into the step kernel itself (step_clock_rec.h: ClockFold) over three rotating slot arrays;

@@ -160,7 +160,7 @@ static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, doub
   (void)current;
   while (done < nsteps && *t < tEnd) {
     const int parity = *nStep % 2;
-    if (!clock_ready(c, parity) || (H && !H->batch) || (M && !monitor_batch_ok(c))) {   // the reference's loop body (the first step of a run always comes through here)
+    if (!clock_ready(c, parity) || (H && !H->batch) || (M && !monitor_scratch_fits(c))) {   // the reference's loop body (the first step of a run always comes through here)
       if (H && hist_batch_due(*t, *dt, *H->tHist, H->dtHist)) {   // ... with the head of MHDRunGodunov.cpp:3975-3984, literally
         const int k = *H->n;
         if (const int rch = rgpu_history_mri(c, parity, H->v + (size_t)k * RGPU_HIST_NQ)) return rch;
@@ -175,7 +175,7 @@ static int run_steps_impl(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, doub
       if (M && *nStep % M->every == 0) {   // the state the step left, U[*nStep % 2]: one synchronisation per sample on this path
         const int k = *M->n;
         double* v = M->v + (size_t)k * RGPU_MON_NQ;
-        if (const int rcm = c->g.three_d ? rgpu_state_monitor3d(c, *nStep & 1, v) : rgpu_state_monitor(c, *nStep & 1, v)) return rcm;
+        if (const int rcm = state_monitor(c, c->g.three_d != 0, *nStep & 1, v)) return rcm;
         M->step[k] = *nStep; M->t[k] = *t;
         *M->n = k + 1;
       }

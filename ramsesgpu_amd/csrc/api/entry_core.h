@@ -321,24 +321,8 @@ int rgpu_state_checksum(rgpu_ctx* c, int parity, unsigned long long* out) {
   return RGPU_OK;
 }
 
-int rgpu_state_monitor(rgpu_ctx* c, int parity, double* out) {
-  RG_CHECK_CTX(c);
-  if (!out || !c->U[0]) return fail(c, RGPU_EINVAL, "state_monitor: null pointer / context without state");
-  if (c->g.three_d) return fail(c, RGPU_EUNSUPPORTED, "state_monitor: 2D contexts only (3D contexts have rgpu_state_monitor3d)");
-  if (!c->F || monitor_scratch_doubles(c->g) > (size_t)c->g.fN * plan_for(c->p).f) return fail(c, RGPU_EINVAL, "state_monitor: no scratch for the segment sums");
-  if (state_monitor(c, parity, out)) return RG_HIPFAIL(c, "state_monitor");
-  return RGPU_OK;
-}
-
-int rgpu_state_monitor3d(rgpu_ctx* c, int parity, double* out) {
-  RG_CHECK_CTX(c);
-  if (!out || !c->U[0]) return fail(c, RGPU_EINVAL, "state_monitor3d: null pointer / context without state");
-  if (!c->g.three_d) return fail(c, RGPU_EUNSUPPORTED, "state_monitor3d: 3D contexts only (2D contexts have rgpu_state_monitor)");
-  if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, "state_monitor3d: single-domain contexts only (a slab holds a part of the box)");
-  if (!monitor3d_scratch_fits(c)) return fail(c, RGPU_EINVAL, "state_monitor3d: no scratch for the partial sums");
-  if (state_monitor3d(c, parity, out)) return RG_HIPFAIL(c, "state_monitor3d");
-  return RGPU_OK;
-}
+int rgpu_state_monitor(rgpu_ctx* c, int parity, double* out) { return state_monitor(c, false, parity, out); }
+int rgpu_state_monitor3d(rgpu_ctx* c, int parity, double* out) { return state_monitor(c, true, parity, out); }
 
 double rgpu_compute_dt(rgpu_ctx* c, int useU) {
   double v = 0;

@@ -8,7 +8,7 @@
 // a table on the device (hip/ensemble_scan.h) instead of handing one member's to the kernels by value.
 // Monitors (kernels_monitor.h): rgpu_ensemble_run_steps_monitored is the same loop with per-member samples of the ten monitor
 // quantities -- on the fused rounds taken by a kernel pair queued inside the batch (hip/ensemble_monitor.h) and read back with the
-// clock records, on the member-by-member rounds by the flat monitor of the member's context.
+// clock records, on the member-by-member rounds by the monitor of the member's context.
 // Here: the object, what it accepts, the loop over rounds and the member-alone path.  The fused half (device buffers, the decision,
 // queueing and harvesting a batch, the device monitor, byte counts) is api/ensemble_fused.h, behind the functions the stand-in below names.
 #pragma once
@@ -143,7 +143,7 @@ struct EnsembleRun {
 namespace {
 bool fused_batch_possible(const EnsembleRun&, const std::vector<int>&, bool* transient, int*, int*) { *transient = false; return false; }
 int fused_batch(EnsembleRun&, const std::vector<int>&, int, int, int, int*) { return RGPU_EUNSUPPORTED; }   // (never called)
-int ensemble_monitor_all(rgpu_ensemble* e, double* out) {   // member by member through the flat monitor
+int ensemble_monitor_all(rgpu_ensemble* e, double* out) {   // member by member through the monitor of a lone context
   for (int m = 0; m < e->members; ++m) {
     rgpu_ctx* c = e->ctx[(size_t)m];
     if (const int rc = rgpu_state_monitor(c, c->cur, out + (size_t)m * MON_NQ)) return efail(e, rc, "ensemble_monitor: member " + std::to_string(m) + ": " + c->err);
@@ -248,7 +248,7 @@ int run_member_alone_plain(EnsembleRun& run, int m, int k) {
   if (r < 0 && why < 2) return efail(run.e, r, "ensemble_run_steps: member " + std::to_string(m) + ": " + c->err);
   return 0;
 }
-// ... sampled: cut at the member's next sampling step, the sample taken by the flat monitor of its context (one synchronisation
+// ... sampled: cut at the member's next sampling step, the sample taken by the monitor of its context (one synchronisation
 // per sample on this path)
 int run_member_alone(EnsembleRun& run, int m, int k) {
   if (!run.mon) return run_member_alone_plain(run, m, k);

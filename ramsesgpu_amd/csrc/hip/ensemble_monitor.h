@@ -6,15 +6,16 @@
 //   ensemble_monitor_rows_kernel   thread (s, ii) of member m: step 1 of the summation order (mon_segment: the rows of segment s of
 //                                  column ii, coalesced in ii) -> part[m][q][s * nx + ii]
 //   ensemble_monitor_fold_kernel   one wave per member: lane l does steps 2 and 3 (mon_lane), the butterfly of step 4 runs across
-//                                  the lanes (__shfl_xor: "L[l] + L[l ^ off]" on every lane, as mon_butterfly does on the host),
-//                                  lane 0 writes the ten doubles to the log slot (launch, m)
-// Both call the functions the flat kernels call, hence the bits of rgpu_state_monitor on a lone context holding that state.
+//                                  the lanes (mon_wave_butterfly, hip/monitor3d.h), lane 0 writes the ten doubles to the log
+//                                  slot (launch, m)
+// Both call the functions the kernels of a lone context call, hence the bits of rgpu_state_monitor on one holding that state.
 // Whether member m is sampled by a launch is decided on the device, in the first instructions of every workgroup, from values that
 // are uniform over the workgroup (scalar loads): inside a batch the record of the round's tick must say that the step ran and the
 // member's own step number after it, span[m].nStep0 + r1, must be a multiple of `every` -- the host queues the pair only for rounds
 // where this can hold for some member and keeps exactly the slots it knows to be valid when it walks the records.
 // dx, dy: by value (g) or, with the table of a parameter scan, member m's own (tab[m].g; the table is read, never written).
 #pragma once
+#include "monitor3d.h"
 
 namespace rgpu_tiled {
 
@@ -44,7 +45,7 @@ __global__ void __launch_bounds__(256) ensemble_monitor_rows_kernel(DevParams g,
   const unsigned par = parity >= 0 ? (unsigned)parity : (unsigned)span[m].parity;
   const double* Um = U + ((size_t)par * members + m) * stride;
   double a[MON_NQ];
-  mon_segment(g, dx, dy, Um, (int)(idx / (unsigned)g.nx), (int)(idx % (unsigned)g.nx), a);
+  mon_segment<false>(g, dx, dy, g.dz, Um, 0, (int)(idx / (unsigned)g.nx), (int)(idx % (unsigned)g.nx), a);
   double* pm = part + (size_t)m * MON_NQ * R;
 #pragma unroll
   for (int q = 0; q < MON_NQ; ++q) pm[(size_t)q * R + idx] = a[q];
@@ -53,19 +54,12 @@ __global__ void __launch_bounds__(256) ensemble_monitor_rows_kernel(DevParams g,
 // out: the log, slot (launch, m) at out[(launch * members + m) * MON_NQ]
 __global__ void __launch_bounds__(MON_LANES) ensemble_monitor_fold_kernel(int nx, int ny, unsigned members, const MonitorSpan* __restrict__ span, const StepClock* clk, int r1,
                                                                           int every, const double* __restrict__ part, double* __restrict__ out, unsigned launch) {
-  static_assert(MON_LANES == 64, "one wave per member");
   const unsigned m = blockIdx.y;
   if (!monitor_samples(span, clk, m, r1, every)) return;
   const int nseg = mon_nseg(ny);
   double a[MON_NQ];
   mon_lane(nx, nseg, part + (size_t)m * MON_NQ * ((size_t)nseg * nx), (int)threadIdx.x, a);
-#pragma unroll
-  for (int off = MON_LANES / 2; off > 0; off >>= 1) {
-    double x[MON_NQ];
-#pragma unroll
-    for (int q = 0; q < MON_NQ; ++q) x[q] = __shfl_xor(a[q], off, 64);
-    mon_combine(a, x);
-  }
+  mon_wave_butterfly(a);
   if (threadIdx.x == 0) {
     double* o = out + ((size_t)launch * members + m) * MON_NQ;
 #pragma unroll

@@ -1,15 +1,17 @@
-// monitor3d.h (HIP / gfx950 only; included from rg_tiled.h) -- the monitor of a 3D state (kernels_monitor.h: mon_vol_*) in three
-// launches, for rgpu_state_monitor3d and for the samples rgpu_run_steps_monitored takes inside its device-clock batches.
+// monitor3d.h (HIP / gfx950 only; included from rg_tiled.h and ensemble_monitor.h) -- the monitor of a lone context's state
+// (kernels_monitor.h), 3D or 2D (a volume of one plane), for rgpu_state_monitor, rgpu_state_monitor3d and the samples
+// rgpu_run_steps_monitored takes inside its device-clock batches.
 //
-//   monitor_vol_cols_kernel     the pass over the state.  Thread ii of segment s (blockIdx.z) of plane kk (blockIdx.y), coalesced in
-//                               ii, walks the rows of the segment in ascending j (mon_vol_segment) -> part[kk][q][s * nx + ii], the
-//                               layout of the 2D rows kernel per plane.  (A thread per whole column, forming C[ii] itself, was
-//                               measured too and lost at every size: DESIGN 3.4.2.)
+//   monitor_vol_cols_kernel     the pass over the state (monitor_plane_cols_kernel: the same body for a 2D state, chosen at launch).
+//                               Thread ii of segment s (blockIdx.z) of plane kk (blockIdx.y), coalesced in
+//                               ii, walks the rows of the segment in ascending j (mon_segment) -> part[kk][q][s * nx + ii].  (A thread
+//                               per whole column, forming C[ii] itself, was measured too and lost at every size: DESIGN 3.4.2.)
 //   monitor_vol_planes_kernel   one wave64 per plane: lane l does steps 2 and 3 (mon_lane), the butterfly runs across the lanes
-//                               (__shfl_xor, as ensemble_monitor_fold_kernel), lane 0 writes V[kk]
+//                               (mon_wave_butterfly), lane 0 writes V[kk]
 //   monitor_vol_finish_kernel   one wave64: V[0] + V[1] + .. in ascending order.  Lane l loads V[k0 + l] of a block of 64 planes (one
 //                               round of loads instead of a chain of nz); every lane then adds the block's planes in order, each
-//                               read from its lane (v_readlane); lane 0 writes out[MON_NQ]
+//                               read from its lane (v_readlane); lane 0 writes out[MON_NQ].  Not launched for one plane, whose V[0]
+//                               is the result bit for bit (kernels_monitor.h): the planes kernel writes it to `out`.
 // All three call the functions the flat functors call.  clk != 0 (inside a batch): the StepClock record of the step the sample
 // follows; a record that says stop ends every workgroup in its first instructions (a uniform scalar load), and the log slot stays
 // unwritten -- the host reads the same record and does not look at it.
@@ -20,24 +22,9 @@ namespace rgpu_tiled {
 
 using namespace rgpu_dev;
 
-__global__ void __launch_bounds__(256) monitor_vol_cols_kernel(DevParams g, const double* __restrict__ U, const StepClock* clk, double* __restrict__ part) {
-  if (!mon_gate_open(clk)) return;
-  const int ii = (int)(blockIdx.x * 256u + threadIdx.x), kk = (int)blockIdx.y, s = (int)blockIdx.z;
-  if (ii >= g.nx) return;
-  double a[MON_NQ];
-  mon_vol_segment(g, U, kk, s, ii, a);
-  const size_t R = (size_t)mon_nseg(g.ny) * g.nx;
-  double* pk = part + (size_t)kk * MON_NQ * R + (size_t)s * g.nx + ii;
-#pragma unroll
-  for (int q = 0; q < MON_NQ; ++q) pk[(size_t)q * R] = a[q];
-}
-
-__global__ void __launch_bounds__(MON_LANES) monitor_vol_planes_kernel(int nx, int nseg, const StepClock* clk, const double* __restrict__ part, double* __restrict__ V) {
-  static_assert(MON_LANES == 64, "one wave per plane");
-  if (!mon_gate_open(clk)) return;
-  const unsigned kk = blockIdx.x;
-  double a[MON_NQ];
-  mon_lane(nx, nseg, part + (size_t)kk * MON_NQ * ((size_t)nseg * nx), (int)threadIdx.x, a);
+// step 4 across the lanes of a wave64 holding L[lane] in a: "L[l] + L[l ^ off]" on every lane; every lane ends with the result
+__device__ __forceinline__ void mon_wave_butterfly(double* a) {
+  static_assert(MON_LANES == 64, "the lanes of the summation order are those of a wave");
 #pragma unroll
   for (int off = MON_LANES / 2; off > 0; off >>= 1) {
     double x[MON_NQ];
@@ -45,6 +32,35 @@ __global__ void __launch_bounds__(MON_LANES) monitor_vol_planes_kernel(int nx, i
     for (int q = 0; q < MON_NQ; ++q) x[q] = __shfl_xor(a[q], off, 64);
     mon_combine(a, x);
   }
+}
+
+template <bool VOL>
+__device__ __forceinline__ void monitor_cols_body(const DevParams& g, const double* __restrict__ U, const StepClock* clk, double* __restrict__ part) {
+  if (!mon_gate_open(clk)) return;
+  const int ii = (int)(blockIdx.x * 256u + threadIdx.x), kk = (int)blockIdx.y, s = (int)blockIdx.z;
+  if (ii >= g.nx) return;
+  double a[MON_NQ];
+  mon_segment<VOL>(g, g.dx, g.dy, g.dz, U, kk, s, ii, a);
+  const size_t R = (size_t)mon_nseg(g.ny) * g.nx;
+  double* pk = part + (size_t)kk * MON_NQ * R + (size_t)s * g.nx + ii;
+#pragma unroll
+  for (int q = 0; q < MON_NQ; ++q) pk[(size_t)q * R] = a[q];
+}
+// the two instantiations, chosen at launch by the dimension of the context (two names: the 3D one keeps the name, the code and the
+// compiler-reported numbers it had)
+__global__ void __launch_bounds__(256) monitor_vol_cols_kernel(DevParams g, const double* __restrict__ U, const StepClock* clk, double* __restrict__ part) {
+  monitor_cols_body<true>(g, U, clk, part);
+}
+__global__ void __launch_bounds__(256) monitor_plane_cols_kernel(DevParams g, const double* __restrict__ U, const StepClock* clk, double* __restrict__ part) {
+  monitor_cols_body<false>(g, U, clk, part);
+}
+
+__global__ void __launch_bounds__(MON_LANES) monitor_vol_planes_kernel(int nx, int nseg, const StepClock* clk, const double* __restrict__ part, double* __restrict__ V) {
+  if (!mon_gate_open(clk)) return;
+  const unsigned kk = blockIdx.x;
+  double a[MON_NQ];
+  mon_lane(nx, nseg, part + (size_t)kk * MON_NQ * ((size_t)nseg * nx), (int)threadIdx.x, a);
+  mon_wave_butterfly(a);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int q = 0; q < MON_NQ; ++q) V[(size_t)kk * MON_NQ + q] = a[q];
@@ -77,17 +93,18 @@ __global__ void __launch_bounds__(64) monitor_vol_finish_kernel(int nz, const St
   }
 }
 
-inline size_t monitor_vol_scratch_doubles(const DevParams& g) { return (size_t)MON_NQ * ((size_t)g.nz * mon_nseg(g.ny) * g.nx + (size_t)g.nz); }
-
-// The three launches; scratch: monitor_vol_scratch_doubles(g) doubles (the segment sums, then V)
+// The launches; scratch: mon_scratch_doubles(g) doubles (the segment sums, then V)
 inline int launch_monitor_vol(rg_stream_t s, const DevParams& g, const double* U, const StepClock* clk, double* scratch, double* out) {
-  const int nseg = mon_nseg(g.ny);
-  double* V = scratch + (size_t)MON_NQ * g.nz * nseg * g.nx;
-  hipLaunchKernelGGL(monitor_vol_cols_kernel, dim3(((unsigned)g.nx + 255u) / 256u, (unsigned)g.nz, (unsigned)nseg), dim3(256), 0, s, g, U, clk, scratch);
+  const int nseg = mon_nseg(g.ny), nz = mon_nplanes(g);
+  double* V = nz == 1 ? out : scratch + (size_t)MON_NQ * nz * nseg * g.nx;
+  const dim3 grid(((unsigned)g.nx + 255u) / 256u, (unsigned)nz, (unsigned)nseg);
+  if (g.three_d) hipLaunchKernelGGL(monitor_vol_cols_kernel, grid, dim3(256), 0, s, g, U, clk, scratch);
+  else hipLaunchKernelGGL(monitor_plane_cols_kernel, grid, dim3(256), 0, s, g, U, clk, scratch);
   if (hipGetLastError() != hipSuccess) return -1;
-  hipLaunchKernelGGL(monitor_vol_planes_kernel, dim3((unsigned)g.nz), dim3(MON_LANES), 0, s, g.nx, nseg, clk, (const double*)scratch, V);
+  hipLaunchKernelGGL(monitor_vol_planes_kernel, dim3((unsigned)nz), dim3(MON_LANES), 0, s, g.nx, nseg, clk, (const double*)scratch, V);
   if (hipGetLastError() != hipSuccess) return -1;
-  hipLaunchKernelGGL(monitor_vol_finish_kernel, dim3(1), dim3(64), 0, s, g.nz, clk, (const double*)V, out);
+  if (nz == 1) return 0;
+  hipLaunchKernelGGL(monitor_vol_finish_kernel, dim3(1), dim3(64), 0, s, nz, clk, (const double*)V, out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -14,6 +14,5 @@
 // the ensemble kernels exist (api/entry_ensemble.h: without this macro -- the test-only host emulation -- an ensemble steps member by member)
 #define RGPU_TILED_ENSEMBLE2D 1
 #include "monitor3d.h"
-// the gfx950 kernels of the 3D monitor exist, and the ensemble's monitor kernels serve a lone 2D context inside its batches
-// (api/monitor.h: without this macro the 3D monitor runs the flat functors and a lone 2D context samples between its steps)
+// the gfx950 kernels of a lone context's monitor exist (api/monitor.h: without this macro it runs the flat functors)
 #define RGPU_TILED_MONITOR3D 1

@@ -1,9 +1,11 @@
-"""Whole-call step rates of a 3D run that takes a monitor sample every `every` steps:
+"""Whole-call step rates of a run, 3D or 2D, that takes a monitor sample every `every` steps:
 
   (a) rgpu_run_steps_monitored on this build: the samples taken on the device inside the device-clock batches, one read-back per batch
   (b) plain rgpu_run_steps on ANOTHER build (--baseline-lib: the parent commit's librgpu_fast.so)
   (c) plain rgpu_run_steps on this build: against (b) it shows what the plain loop pays for the feature (nothing)
-  (d) this build looping rgpu_run_steps(every) + rgpu_state_monitor3d: one synchronisation per sample
+  (d) this build looping rgpu_run_steps(every) + rgpu_state_monitor[3d]: one synchronisation per sample
+  (e) this build calling rgpu_state_monitor[3d] alone, again and again: cells monitored per second
+  --baseline-all: (a), (d) and (e) on the other build as well, for a change that must leave every mode as fast as it was
 
     python scripts/monitor_bench.py [--baseline-lib OLD/librgpu_fast.so] [--out profiles/monitor3d_bench.json]
 
@@ -29,6 +31,10 @@ WORKLOADS = {
     "implode3d-256": ("implode3d", "mesh.nx=256;mesh.ny=256;mesh.nz=256"),
     "mri-64x128x64": ("mhd_mri_3d", "mesh.nx=64;mesh.ny=128;mesh.nz=64"),
     "mri-256": ("mhd_mri_3d", "mesh.nx=256;mesh.ny=256;mesh.nz=256"),
+    "kh2d-512": ("kelvin_helmholtz_gpu_2d", "mesh.nx=512;mesh.ny=512"),
+    "kh2d-2048": ("kelvin_helmholtz_gpu_2d", "mesh.nx=2048;mesh.ny=2048"),
+    "ot2d-512": ("orszag-tang", "mesh.nx=512;mesh.ny=512"),
+    "ot2d-2048": ("orszag-tang", "mesh.nx=2048;mesh.ny=2048"),
 }
 
 
@@ -51,6 +57,11 @@ class Run:
             self.samples += len(s.step)
         elif self.mode == "c":
             done = sv.run_steps(k)
+        elif self.mode == "e":
+            for _ in range(k):
+                sv.state_monitor()
+            self.samples += k
+            done = k
         else:
             done = 0
             while done < k:
@@ -73,6 +84,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arith", default="contracted", choices=["exact", "contracted"])
     ap.add_argument("--baseline-lib", default=None, help="another build of the library (the parent commit's): plain rgpu_run_steps on it is mode (b)")
+    ap.add_argument("--baseline-all", action="store_true", help="modes (a) and (d) on the baseline library too (it must have them)")
     ap.add_argument("--workloads", default="implode3d-64,mri-64x128x64,implode3d-256,mri-256")
     ap.add_argument("--every", type=int, default=10)
     ap.add_argument("--reverse", action="store_true", help="create the contexts of the modes in the opposite order")
@@ -90,7 +102,11 @@ def main():
         makers = [("a_run_steps_monitored", lambda: Run(lib, base, ov, "a", a.every))]
         if base_lib:
             makers.append(("b_run_steps_baseline", lambda: Run(base_lib, base, ov, "c", a.every)))
-        makers += [("c_run_steps", lambda: Run(lib, base, ov, "c", a.every)), ("d_loop_state_monitor3d", lambda: Run(lib, base, ov, "d", a.every))]
+        if base_lib and a.baseline_all:
+            makers += [("a_baseline", lambda: Run(base_lib, base, ov, "a", a.every)), ("d_baseline", lambda: Run(base_lib, base, ov, "d", a.every)),
+                       ("e_baseline", lambda: Run(base_lib, base, ov, "e", a.every))]
+        makers += [("c_run_steps", lambda: Run(lib, base, ov, "c", a.every)), ("d_loop_state_monitor3d", lambda: Run(lib, base, ov, "d", a.every)),
+                   ("e_state_monitor_alone", lambda: Run(lib, base, ov, "e", a.every))]
         modes = {name: make() for name, make in (makers[::-1] if a.reverse else makers)}
         steps = {name: max(a.every, calibrate(mode, a.window) // a.every * a.every) for name, mode in modes.items()}
         rates, secs = {name: [] for name in modes}, {name: [] for name in modes}
@@ -116,6 +132,12 @@ def main():
             bm = row["b_run_steps_baseline"]
             row["c_within_b_min_max"] = bm["min"] <= cm["median"] <= bm["max"]
             row["a_over_b"] = am["median"] / bm["median"]
+            # no slower than the baseline's median by more than the baseline's own spread (max - min of its windows), mode by mode
+            for name, other in (("a_run_steps_monitored", "a_baseline"), ("c_run_steps", "b_run_steps_baseline"), ("d_loop_state_monitor3d", "d_baseline"), ("e_state_monitor_alone", "e_baseline")):
+                if other in row:
+                    o = row[other]
+                    row[name + "_over_baseline"] = row[name]["median"] / o["median"]
+                    row[name + "_holds"] = row[name]["median"] >= o["median"] - (o["max"] - o["min"])
         row["a_over_c"] = am["median"] / cm["median"]
         for mode in modes.values():
             mode.close()

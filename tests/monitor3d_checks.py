@@ -84,6 +84,52 @@ def initial_state(lib, base, ov, p):
     return ec.member_states(lib, base, ov, p, 1)[0]
 
 
+# 2D shapes (nx, ny) at the seams of the summation order: a lane without a column and a short segment; exactly full lanes and one full
+# segment; one column into the second round of the lanes and one row into a second segment; the same one round and one segment later
+SEAM_SHAPES = [(63, 31), (64, 32), (65, 33), (130, 65)]
+SEAMS = [(base, "mesh.nx=%d;mesh.ny=%d" % s) for s in SEAM_SHAPES for base in ("kelvin_helmholtz_gpu_2d", "orszag-tang")]
+
+
+def check_seam_state(lib, base, ov):
+    """a lone 2D context before stepping and after 3 steps: rgpu_state_monitor == the model on its download == rgpu_ensemble_monitor
+    of a one-member ensemble holding that state (uploaded, so that it is the same state in either library), bit for bit"""
+    from ramsesgpu_amd.ensemble import Ensemble
+    p = lib.params_from_ini(ec.ini(base), ov)
+    assert not is3d(p) and p.mhdEnabled == (base == "orszag-tang") and (p.mhdEnabled or p.nbVar == 4)
+    sv, ens = Solver(p, lib), Ensemble(p, 1, lib)
+    try:
+        sv.start(initial_state(lib, base, ov, p), 0)
+        for steps in (0, 3):
+            if steps:
+                assert sv.run_steps(steps) == steps
+            got, U = sv.state_monitor(), sv.getDataHost()
+            print(base, ov, "after %d steps:" % steps, dict(zip(_capi.MON_NAMES, got)))
+            assert np.array_equal(got, mc.model(U, p)), (got, mc.model(U, p))
+            ens.member(0).upload(U)
+            one = ens.monitor()
+            assert one.shape == (1, NQ) and np.array_equal(one[0], got), (one[0], got)
+    finally:
+        ens.close()
+        sv.close()
+
+
+def check_seam_nan(lib, base, ov):
+    """the NaN rules on a seam shape: one NaN density in the last column of the last row (the short lane, the short segment)"""
+    p = lib.params_from_ini(ec.ini(base), ov)
+    U0 = initial_state(lib, base, ov, p)
+    gw = p.ghostWidth
+    U0[0, 0, gw + p.ny - 1, gw + p.nx - 1] = np.nan
+    sv = Solver(p, lib)
+    try:
+        sv.upload(U0)
+        got = sv.state_monitor(0)
+        assert_nan_rules(got, U0, p)
+        assert np.isnan(got[0]) and np.isnan(got[5]) and not np.isnan(got[1]) and not np.isnan(got[4]) and np.isfinite(got[7:]).all()
+        assert np.array_equal(got, mc.model(U0, p), equal_nan=True)
+    finally:
+        sv.close()
+
+
 _STEPPED = {}   # (library path, base, ov, end time): {"sv": a lone Solver at step n, "at": {n: (monitor, model, t)}} -- computed once, shared, left alone
 
 

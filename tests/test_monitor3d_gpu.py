@@ -74,6 +74,25 @@ def test_samples_inside_the_device_batches(base, ov, every, lib):
     assert batch == len(steps) - (1 if every == 1 else 0) or (base, ov) == FOLDED
 
 
+@pytest.mark.parametrize("base,ov", m3.SEAMS, ids=ids(m3.SEAMS))
+def test_2d_shapes_at_the_seams_of_the_summation_order(base, ov, lib):
+    """a 2D state is a volume of one plane (csrc/hip/monitor3d.h without its finish launch) at shapes where a lane, a round of the lanes
+    or a segment begins or ends: against the model and the ensemble kernels, and every sample taken inside a batch against a second
+    context stepped singly"""
+    m3.check_seam_state(lib, base, ov)
+    def want(done, ready):   # steps 2 .. 6 follow the first, plain step: on the device path, all five samples are taken inside batches
+        print(base, ov, "device path after the run:", ready)
+        assert ready == 1, "the context does not take its time step from the device"
+        return done - 1
+    done, steps, vals, batch = m3.check_monitored_lone(lib, base, ov, 6, 1, expect_batch=want)
+    assert done == 6 and steps == [1, 2, 3, 4, 5, 6] and batch == 5
+
+
+def test_nan_cell_on_a_seam_shape(lib):
+    for base, ov in m3.SEAMS[4:6]:   # 65 x 33, hydro and MHD
+        m3.check_seam_nan(lib, base, ov)
+
+
 @pytest.mark.parametrize("base,ov", [BATCHED[0], BATCHED[2], BATCHED[4]], ids=ids([BATCHED[0], BATCHED[2], BATCHED[4]]))
 def test_run_in_pieces(base, ov, lib):
     """[4, 6]: step 1 is plain, the second call begins on the device path -- samples 3, 6, 9 all inside batches"""

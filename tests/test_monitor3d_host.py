@@ -142,6 +142,17 @@ def test_monitored_run(base, ov, every, emu_lib):
         assert (batch > 0) == three_d   # the emulation runs the 3D device-clock batches; its 2D steps take their dt from the host
 
 
+@pytest.mark.parametrize("base,ov", m3.SEAMS, ids=ids(m3.SEAMS))
+def test_2d_shapes_at_the_seams_of_the_summation_order(base, ov, emu_lib):
+    """a 2D state is a volume of one plane: the flat functors at shapes where a lane, a round of the lanes or a segment begins or ends"""
+    m3.check_seam_state(emu_lib, base, ov)
+
+
+def test_nan_cell_on_a_seam_shape(emu_lib):
+    for base, ov in m3.SEAMS[4:6]:   # 65 x 33, hydro and MHD
+        m3.check_seam_nan(emu_lib, base, ov)
+
+
 def test_gravity_takes_the_literal_loop(emu_lib):
     base, ov = GRAVITY
     done, steps, vals, batch = m3.check_monitored_lone(emu_lib, base, ov, 10, 3, pieces=[4, 6])

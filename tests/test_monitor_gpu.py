@@ -32,7 +32,7 @@ def setup(lib, base, ov, members):
 
 @pytest.mark.parametrize("base,ov", [(OT, "mesh.nx=24;mesh.ny=40"), (KH, KH_SIZE)], ids=[OT, KH])
 def test_state_monitor_equals_the_model(base, ov, lib):
-    """the flat kernels on the device: after 0 and 3 steps, bit for bit the numpy model in both libraries"""
+    """the kernels of a lone context on the device: after 0 and 3 steps, bit for bit the numpy model in both libraries"""
     p, (U0,) = setup(lib, base, ov, 1)
     sv = Solver(p, lib)
     try:
@@ -58,7 +58,7 @@ def test_fused_rounds_are_sampled_on_the_device(base, ov, members, every, lib):
     assert done == [N] * members and stop == [0] * members
     assert [s[0] for s in series] == [[n for n in range(1, N + 1) if n % every == 0]] * members
     if fused_expected(lib):
-        assert fused == N - 1   # the first step of a run is the plain one: its sample (every == 1) comes from the flat monitor
+        assert fused == N - 1   # the first step of a run is the plain one: its sample (every == 1) comes from the monitor of the member's context
 
 
 def test_members_with_different_step_counts(lib):
@@ -121,7 +121,7 @@ def test_scan_members_take_their_own_dx(lib):
 
 
 def test_uncovered_configuration_is_sampled_member_by_member(lib):
-    """2D MHD with Neumann faces: no fused round; the samples come from the flat monitor of each member's context"""
+    """2D MHD with Neumann faces: no fused round; the samples come from the monitor of each member's context"""
     base, ov = "mhd_BrioWu", "mesh.nx=128;mesh.ny=8"
     p, U0s = setup(lib, base, ov, 3)
     done, stop, fused, series = mc.check_monitored(lib, [p] * 3, U0s, 6, 2, exact=exact(lib))
