@@ -1,5 +1,6 @@
 // api/ctx.h -- the context of the C ABI (struct rgpu_ctx), parameter validation, allocation, creation.  Part of the ONE translation
-// unit rgpu_api.cpp (included there, in this order: ctx, boundaries, step, history, monitor, forcing, then the entry points).
+// unit rgpu_api.cpp (included there, in this order: ctx, boundaries, step, history, monitor, forcing, then the entry points: core,
+// clock, run_steps, ensemble, misc).
 #pragma once
 // every entry point makes the context's device current: a multi-GPU process (or a thread whose current device differs)
 // would otherwise launch on the wrong device
@@ -33,59 +34,77 @@ class StateRecord {
   int scan_ = -1, nslots_ = 1, acc_ = -1, ghosts_ = -1;
 };
 
+// a device buffer and, unless left out, as many elements again in pinned host memory: both or neither.  Freed with its owner, whose
+// device must be current then (rgpu_destroy, rgpu_ensemble_destroy)
+template <class T>
+struct DeviceMirror {
+  T *d = 0, *h = 0;
+  DeviceMirror() = default;
+  DeviceMirror(const DeviceMirror&) = delete;
+  ~DeviceMirror() { release(); }
+  bool allocated() const { return d != 0; }
+  int alloc(size_t n, bool mirror = true) {   // != 0: failed, nothing is left allocated
+    if (rg_malloc((void**)&d, n * sizeof(T)) || (mirror && rg_host_alloc((void**)&h, n * sizeof(T)))) { release(); return -1; }
+    return 0;
+  }
+  void release() { rg_free(d); d = 0; if (h) rg_host_free(h); h = 0; }
+  int upload(size_t n, rg_stream_t s) { return rg_copy_h2d(d, h, n * sizeof(T), s); }
+  int download(size_t n, rg_stream_t s) { return rg_copy_d2h(h, d, n * sizeof(T), s); }
+};
+
+// (what a member's initialiser leaves out depends on the arguments of create_common, or is set before it is read)
 struct rgpu_ctx {
-  rgpu_params p;
-  DevParams g;
-  rg_stream_t stream;
-  bool own_state;
-  double* U[2];
-  double *Q, *E, *T, *F, *emf, *shear_save, *shear_remap;
-  double* G;   // per-cell static gravity field (gravityEnabled == 2), 3 components
-  double* Frc; // static driving field of the "turbulence" problem (randomForcingEnabled), 3 components
-  rgpu_ou::OuProcess* ou;   // Ornstein-Uhlenbeck forcing process (ouForcingEnabled)
-  unsigned long long* d_red;
-  unsigned long long* h_red;
-  size_t ncell, scratch_bytes;
-  unsigned n32;
+  rgpu_params p = {};
+  DevParams g = {};
+  rg_stream_t stream = (rg_stream_t)0;
+  bool own_state = true;
+  double* U[2] = {0, 0};
+  double *Q = 0, *E = 0, *T = 0, *F = 0, *emf = 0, *shear_save = 0, *shear_remap = 0;
+  double* G = 0;   // per-cell static gravity field (gravityEnabled == 2), 3 components
+  double* Frc = 0; // static driving field of the "turbulence" problem (randomForcingEnabled), 3 components
+  rgpu_ou::OuProcess* ou = 0;   // Ornstein-Uhlenbeck forcing process (ouForcingEnabled)
+  unsigned long long* d_red = 0;
+  unsigned long long* h_red = 0;
+  size_t ncell = 0, scratch_bytes = 0;
+  unsigned n32 = 0;
   // instrumentation
-  bool timers_on;
-  double t_acc[RGPU_T_COUNT];
-  long t_calls[RGPU_T_COUNT];
+  bool timers_on = false;
+  double t_acc[RGPU_T_COUNT] = {};
+  long t_calls[RGPU_T_COUNT] = {};
   rg_event_t ev0, ev1;
-  bool ev_ok;
+  bool ev_ok = false;
   // z-chunked two-stream schedule of the 3D MHD step (mhd3d_core_overlap)
   enum { kMaxChunks = 256 };
-  int nchunks;
-  rg_stream_t stream2;
+  int nchunks = 1;
+  rg_stream_t stream2 = (rg_stream_t)0;
   rg_event_t ev_fork, ev_trace[kMaxChunks], ev_flux[kMaxChunks];
-  int n_order_events;   // ev_trace / ev_flux pairs actually created (freed in rgpu_destroy whatever nchunks became)
-  bool fork_ok;
-  int device;           // HIP device the context was created on; every entry point makes it current
-  unsigned xcd_sub;     // sub-band size (cells) of the XCD-aware workgroup order of THIS context, 0 = linear
-  StateRecord rec;      // what the slots d_red and the ghost cells hold of U[0], U[1]
-  // device-side time step (hip/step_clock.h; rgpu_run_steps): records of a batch on the device / pinned host memory, and the record the
+  int n_order_events = 0;   // ev_trace / ev_flux pairs actually created (freed in rgpu_destroy whatever nchunks became)
+  bool fork_ok = false;
+  int device = -1;          // HIP device the context was created on; every entry point makes it current
+  unsigned xcd_sub = 4096;  // sub-band size (cells) of the XCD-aware workgroup order of THIS context, 0 = linear
+  StateRecord rec;          // what the slots d_red and the ghost cells hold of U[0], U[1]
+  // device-side time step (hip/step_clock.h; rgpu_run_steps): records of a batch on the device / in pinned host memory, and the record the
   // step being queued reads (0: the step takes its by-value dt arguments)
   enum { kClockBatch = RGPU_CLOCK_BATCH };
-  StepClock* d_clk; StepClock* h_clk; const StepClock* clk_cur;
-  int clk_n;                    // records queued in the open batch (rgpu_clock_open .. rgpu_clock_close), -1: no batch open
-  double clk_t0, clk_tEnd;
-  // the history rows sampled inside a batch (kernels_history.h; rgpu_run_steps_history): one record per step of a batch on the device /
-  // in pinned host memory, allocated by the first call that needs them
-  HistBatchRec* d_hist; HistBatchRec* h_hist;
-  long hist_heads;              // history heads queued on the device so far (rgpu_history_batch_heads: lets a caller tell which path ran)
-  // the monitor samples taken inside a batch (kernels_monitor.h; rgpu_run_steps_monitored): kClockBatch slots of MON_NQ doubles on the
-  // device / in pinned host memory, allocated by the first call that needs them
-  double* d_mon; double* h_mon;
-  long mon_samples;             // monitor samples queued on the device so far (rgpu_monitor_batch_samples)
+  DeviceMirror<StepClock> clk; const StepClock* clk_cur = 0;
+  int clk_n = -1;               // records queued in the open batch (rgpu_clock_open .. rgpu_clock_close), -1: no batch open
+  double clk_t0 = 0.0, clk_tEnd = 0.0;
+  // the history rows sampled inside a batch (kernels_history.h; rgpu_run_steps_history): one record per step of a batch, allocated by
+  // the first call that needs them
+  DeviceMirror<HistBatchRec> hist;
+  long hist_heads = 0;          // history heads queued on the device so far (rgpu_history_batch_heads: lets a caller tell which path ran)
+  // the monitor samples taken inside a batch (kernels_monitor.h; rgpu_run_steps_monitored): kClockBatch slots of MON_NQ doubles,
+  // allocated by the first call that needs them
+  DeviceMirror<double> mon;
+  long mon_samples = 0;         // monitor samples queued on the device so far (rgpu_monitor_batch_samples)
   // fused 2D steps: the clock is folded into the step kernel itself (step_clock_rec.h: ClockFold) over three rotating slot arrays;
   // d_red always points at the array that holds the maxima of the current state
-  unsigned long long* d_red_base;   // 3 x RG_DT_SLOTS
-  bool fold_mode, fold_pending; int fold_phase0; ClockFold fold;
-  bool fold_request;            // set by rgpu_run_steps_log around its own rgpu_clock_open (clock_ready holds there): a batch opened from outside never folds
-  int cur;                      // parity of the array that holds the current state: 0 after rgpu_upload, (nStep + 1) % 2 after a step taken through
+  unsigned long long* d_red_base = 0;   // 3 x RG_DT_SLOTS
+  bool fold_mode = false, fold_pending = false; int fold_phase0 = 0; ClockFold fold;
+  int cur = 0;                  // parity of the array that holds the current state: 0 after rgpu_upload, (nStep + 1) % 2 after a step taken through
                                 // rgpu_godunov_unsplit / rgpu_one_step_integration, nStep % 2 after rgpu_run_steps* (what rgpu_ensemble_monitor reports; the staged
                                 // rgpu_step_* pieces do not move it: include/rgpu.h says so)
-  bool borrowed;                // member of an rgpu_ensemble (api/entry_ensemble.h): state and slot arrays are slices of the ensemble's, rgpu_destroy refuses
+  bool borrowed = false;        // member of an rgpu_ensemble (api/entry_ensemble.h): state and slot arrays are slices of the ensemble's, rgpu_destroy refuses
   std::string err;
 };
 
@@ -255,26 +274,8 @@ int create_common(const rgpu_params* p, double* dU, double* dU2, void* hip_strea
   rgpu_ctx* c = new (std::nothrow) rgpu_ctx();
   if (!c) return RGPU_ENOMEM;
   *out = c;  // returned even on failure so that rgpu_last_error can be read; caller destroys it
-  std::memset(&c->p, 0, sizeof(c->p));
   if (p) c->p = *p;
   c->own_state = !external;
-  c->borrowed = false;
-  c->cur = 0;
-  c->U[0] = c->U[1] = 0;
-  c->Q = c->E = c->T = c->F = c->emf = c->shear_save = c->shear_remap = 0;
-  c->G = 0;
-  c->Frc = 0;
-  c->ou = 0;
-  c->d_red = 0; c->d_red_base = 0; c->fold_mode = false; c->fold_request = false; c->fold_pending = false; c->fold_phase0 = 0; c->h_red = 0; c->d_clk = 0; c->h_clk = 0; c->d_hist = 0; c->h_hist = 0; c->hist_heads = 0; c->d_mon = 0; c->h_mon = 0; c->mon_samples = 0; c->clk_cur = 0; c->clk_n = -1; c->clk_t0 = 0.0; c->clk_tEnd = 0.0;
-  c->scratch_bytes = 0;
-  c->timers_on = false; c->ev_ok = false;
-  for (int i = 0; i < RGPU_T_COUNT; ++i) { c->t_acc[i] = 0; c->t_calls[i] = 0; }
-  c->stream = (rg_stream_t)0;
-  c->stream2 = (rg_stream_t)0;
-  c->nchunks = 1;
-  c->n_order_events = 0; c->fork_ok = false;
-  c->device = -1;
-  c->xcd_sub = 4096;
   if (vr) return fail(c, vr, why);
   if (rg_device_count() < 1) return fail(c, RGPU_ENODEVICE, "no HIP device: this library has no CPU fallback (backend " RG_BACKEND_NAME ")");
   c->device = rg_current_device();
@@ -321,7 +322,6 @@ int create_common(const rgpu_params* p, double* dU, double* dU2, void* hip_strea
     return fail(c, RGPU_ENOMEM, "allocation of the reduction slots failed");
   c->d_red = c->d_red_base;
   if (rg_event_create(&c->ev0) == 0 && rg_event_create(&c->ev1) == 0) c->ev_ok = true;
-  c->nchunks = 1;
   // sub-band size (cells) of the XCD-aware workgroup order, 0 = linear order (rg_backend.h: rg_launch_planes)
   if (rgpu::options().xcd_sub >= 0) c->xcd_sub = (unsigned)rgpu::options().xcd_sub;
   c->g.xcd_sub = (int)c->xcd_sub;

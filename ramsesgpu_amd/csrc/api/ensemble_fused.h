@@ -154,7 +154,7 @@ int fused_batch_harvest(EnsembleRun& run, const std::vector<int>& R, const Fused
     if (r < b.queued) {   // its later steps were no-ops: the state of step n0 + r is the last one written, slots and ghost cells are still its
       run.code[m] = rec[(size_t)r * M].stop;
       c->rec.stopped_at((n0 + r) % 2, true);
-      if (run.code[m] >= 2) c->err = run.code[m] == 2 ? "run_steps: the time step is not a number" : "run_steps: 1/dt is not finite";
+      if (run.code[m] >= 2) c->err = stop_message(run.code[m]);
     }
   }
   run.fused += advanced;

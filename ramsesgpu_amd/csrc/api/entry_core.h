@@ -15,17 +15,11 @@ void rgpu_destroy(rgpu_ctx* c) {
   rg_free(c->Q); rg_free(c->E); rg_free(c->T); rg_free(c->F); rg_free(c->emf); rg_free(c->shear_save); rg_free(c->shear_remap); rg_free(c->G); rg_free(c->Frc);
   delete c->ou;
   rg_free(c->d_red_base); rg_host_free(c->h_red);
-  if (c->d_clk) rg_free(c->d_clk);
-  if (c->h_clk) rg_host_free(c->h_clk);
-  if (c->d_hist) rg_free(c->d_hist);
-  if (c->h_hist) rg_host_free(c->h_hist);
-  if (c->d_mon) rg_free(c->d_mon);
-  if (c->h_mon) rg_host_free(c->h_mon);
   if (c->ev_ok) { rg_event_destroy(c->ev0); rg_event_destroy(c->ev1); }
   if (c->fork_ok) rg_event_destroy(c->ev_fork);
   for (int i = 0; i < c->n_order_events; ++i) { rg_event_destroy(c->ev_trace[i]); rg_event_destroy(c->ev_flux[i]); }
   if (c->stream2) rg_stream_destroy(c->stream2);
-  delete c;
+  delete c;   // (with the records and logs of its batches: DeviceMirror, on the device made current above)
 }
 
 size_t rgpu_device_bytes(const rgpu_params* p) {

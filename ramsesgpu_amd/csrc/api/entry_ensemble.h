@@ -15,27 +15,10 @@
 
 namespace {
 const rg_stream_t kStream = (rg_stream_t)0;   // the ensemble's one stream: the one rgpu_create gives a lone context
-
-// a device buffer and, unless left out, as many elements again in pinned host memory: both or neither
-template <class T>
-struct DeviceMirror {
-  T *d = 0, *h = 0;
-  DeviceMirror() = default;
-  DeviceMirror(const DeviceMirror&) = delete;
-  ~DeviceMirror() { release(); }
-  bool allocated() const { return d != 0; }
-  int alloc(size_t n, bool mirror = true) {   // != 0: failed, nothing is left allocated
-    if (rg_malloc((void**)&d, n * sizeof(T)) || (mirror && rg_host_alloc((void**)&h, n * sizeof(T)))) { release(); return -1; }
-    return 0;
-  }
-  void release() { rg_free(d); d = 0; if (h) rg_host_free(h); h = 0; }
-  int upload(size_t n, rg_stream_t s) { return rg_copy_h2d(d, h, n * sizeof(T), s); }
-  int download(size_t n, rg_stream_t s) { return rg_copy_d2h(h, d, n * sizeof(T), s); }
-};
 }  // namespace
 
 #ifdef RGPU_TILED_ENSEMBLE2D
-// What the fused rounds (api/ensemble_fused.h) keep on the device: each allocated by the first caller that needs it, freed with the ensemble
+// What the fused rounds (api/ensemble_fused.h) keep on the device (DeviceMirror: api/ctx.h): each allocated by the first caller that needs it, freed with the ensemble
 struct EnsembleFused {
   DeviceMirror<StepClock> clk;                  // records of a batch, tick-major: tick n of member m at [n * members + m]
   DeviceMirror<rgpu_tiled::EnsembleSpan> span;
@@ -231,8 +214,9 @@ namespace {
 int run_member_alone_plain(EnsembleRun& run, int m, int k) {
   rgpu_ctx* c = run.e->ctx[(size_t)m];
   const int n0 = run.nStep[m];
-  int why = 0;
-  const int r = run_steps_impl(c, k, run.end_of(m), run.nStep + m, run.t + m, run.dt + m, run.dt_log ? run.dt_log + (size_t)m * run.nsteps + run.done[m] : 0, &why);
+  LoneRun lone = {c, k, run.end_of(m), run.nStep + m, run.t + m, run.dt + m, run.dt_log ? run.dt_log + (size_t)m * run.nsteps + run.done[m] : 0, 0, 0};
+  const int r = run_steps_impl(lone);
+  int why = lone.why;
   run.done[m] += run.nStep[m] - n0;
   if (r == RGPU_EHIP && !why) {
     // a plain step of the single-context loop failed: was it a time step that is not a number (nothing was launched then and the
@@ -241,7 +225,7 @@ int run_member_alone_plain(EnsembleRun& run, int m, int k) {
     double inv = 0.0;
     if (rgpu_compute_inv_dt(c, run.nStep[m] % 2, &inv) == RGPU_OK && !(c->p.cfl / inv == c->p.cfl / inv)) {
       why = 2;
-      c->err = "run_steps: the time step is not a number";
+      c->err = stop_message(why);
     }
   }
   if (why) run.code[m] = why;

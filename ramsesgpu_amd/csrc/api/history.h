@@ -51,7 +51,7 @@ int history_turbulence_columns(rgpu_ctx* c, int parity, double* h_cols) {
 
 // ---- the history row of a step inside a batch of device-clock steps (kernels_history.h) -----------------------------
 // Queues, behind the tick of the step `nStep` (record c->clk_cur, the `slot`-th of the open batch), the five launches that take the
-// row of rgpu_history_mri of U[nStep % 2] when the loop's condition holds for this step, and write d_hist[slot] either way.
+// row of rgpu_history_mri of U[nStep % 2] when the loop's condition holds for this step, and write record `slot` of the log (c->hist) either way.
 // dt0, tHist0: the loop's *dt and *tHist at the head of the batch's first step (read by slot 0 only).
 // Scratch in F exactly as hist_scratch lays it out (the Reynolds column sums go where the vx sums were).  F is dead here: the
 // step before is complete in stream order (a batch is queued on the context stream alone: mhd3d_core is `serial` while c->clk_cur
@@ -63,14 +63,14 @@ int history_batch_queue(rgpu_ctx* c, int nStep, int slot, double dt0, double tHi
   const size_t is = (size_t)c->g.isize;
   double* rcol = h.cols + is;   // column 1 (the vx sums) has served once the means are formed
   const double* U = c->U[nStep & 1];
-  const HistBatchGate gate = {c->clk_cur, slot ? c->d_clk + slot - 1 : 0, slot ? c->d_hist + slot - 1 : 0, dt0, tHist0, dtHist};
+  const HistBatchGate gate = {c->clk_cur, slot ? c->clk.d + slot - 1 : 0, slot ? c->hist.d + slot - 1 : 0, dt0, tHist0, dtHist};
   const double dTau = rgpu_hist::dtau(c->p);
   const int nyz = c->p.ny * (c->g.three_d ? c->p.nz : 1);
   K_hist_batch_gated<K_hist_rows> k1 = {gate, {c->g, U, h.rows}};
   K_hist_batch_cols k2 = {gate, {c->g, h.rows, h.cols, HIST_NQ}, h.mean, nyz};
   K_hist_batch_gated<K_hist_reynolds> k3 = {gate, {c->g, U, h.mean, h.mean + is, dTau, h.rows}};
   K_hist_batch_gated<K_hist_cols> k4 = {gate, {c->g, h.rows, rcol, 1}};
-  K_hist_batch_finish k5 = {gate, c->g.isize, c->g.gw, h.cols, rcol, dTau, nStep, c->d_hist + slot};
+  K_hist_batch_finish k5 = {gate, c->g.isize, c->g.gw, h.cols, rcol, dTau, nStep, c->hist.d + slot};
   if (rg_launch<kBlock>(c->stream, (unsigned)h.R, k1) || rg_launch<kBlock>(c->stream, (unsigned)(HIST_NQ * is), k2) ||
       rg_launch<kBlock>(c->stream, (unsigned)h.R, k3) || rg_launch<kBlock>(c->stream, (unsigned)is, k4) ||
       rg_launch<64>(c->stream, (unsigned)HIST_BATCH_NQ, k5)) return -1;

@@ -47,19 +47,15 @@ int state_monitor(rgpu_ctx* c, bool want3d, int parity, double* out) {
 
 // ---- the samples of a batch -------------------------------------------------------------------------------------------------------
 int monitor_batch_alloc(rgpu_ctx* c) {
-  if (c->d_mon) return 0;
-  const size_t bytes = (size_t)rgpu_ctx::kClockBatch * MON_NQ * sizeof(double);
-  if (rg_malloc((void**)&c->d_mon, bytes) || rg_host_alloc((void**)&c->h_mon, bytes) || rg_memset_async(c->d_mon, 0, bytes, c->stream)) {
-    if (c->d_mon) { rg_free(c->d_mon); c->d_mon = 0; }
-    if (c->h_mon) { rg_host_free(c->h_mon); c->h_mon = 0; }
-    return -1;
-  }
-  return 0;
+  const size_t n = (size_t)rgpu_ctx::kClockBatch * MON_NQ;
+  if (c->mon.allocated() || (c->mon.alloc(n) == 0 && rg_memset_async(c->mon.d, 0, n * sizeof(double), c->stream) == 0)) return 0;
+  c->mon.release();   // zeroed, or not there
+  return -1;
 }
 // Queues, behind the last kernel of the step whose record is c->clk_cur (the `slot`-th of the open batch), the sample of U[parity],
-// the state that step leaves: into d_mon[slot] if the record says that the step ran.
+// the state that step leaves: into slot `slot` of the log if the record says that the step ran.
 int monitor_batch_queue(rgpu_ctx* c, int parity, int slot) {
-  const int rc = monitor_queue(c, c->U[parity & 1], c->clk_cur, c->d_mon + (size_t)slot * MON_NQ);
+  const int rc = monitor_queue(c, c->U[parity & 1], c->clk_cur, c->mon.d + (size_t)slot * MON_NQ);
   if (rc == 0) ++c->mon_samples;
   return rc;
 }

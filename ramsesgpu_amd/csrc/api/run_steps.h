@@ -1,0 +1,210 @@
+// api/run_steps.h -- entry points: the time loop of a lone context (rgpu_run_steps, _log, _history, _monitored; every member-alone round
+// of an ensemble comes through here too).  One LoneRun per call; per turn either the reference's loop body (literal_turn) or a batch
+// of device-clock steps (api/entry_clock.h), queued by batch_queue and read back once by batch_harvest.  The two optional consumers
+// of a step -- the history row in front of it, the monitor sample behind it -- each write the caller's arrays in one place, put().
+#pragma once
+
+namespace {
+// what rgpu_run_steps_history adds to the loop: the history cadence and where the samples go (see include/rgpu.h)
+struct HistRun {
+  double dtHist; double* tHist;
+  int* n; int* step; double* t; double* dt; double* v;   // *n samples so far; step[k], t[k], dt[k], v[k][RGPU_HIST_NQ]
+  bool batch;                                            // option "history_batch": sample on the device inside the device-clock batches
+  void put(int step_no, double ts, double dts, const double* row) const {
+    const int k = (*n)++;
+    step[k] = step_no; t[k] = ts; dt[k] = dts;
+    std::memcpy(v + (size_t)k * RGPU_HIST_NQ, row, RGPU_HIST_NQ * sizeof(double));
+  }
+};
+static_assert((int)HIST_BATCH_NQ == RGPU_HIST_NQ, "include/rgpu.h states the width of a history row");
+
+// what rgpu_run_steps_monitored adds to the loop: the cadence in steps and where the samples go (see include/rgpu.h)
+struct MonRun {
+  int every;
+  int* n; int* step; double* t; double* v;   // *n samples so far; step[k], t[k], v[k][RGPU_MON_NQ]
+  bool due(int step_no) const { return step_no % every == 0; }   // the state step number step_no names is sampled
+  void put(int step_no, double ts, const double* values) const {
+    const int k = (*n)++;
+    step[k] = step_no; t[k] = ts;
+    std::memcpy(v + (size_t)k * RGPU_MON_NQ, values, RGPU_MON_NQ * sizeof(double));
+  }
+};
+
+// One call of rgpu_run_steps*: the caller's arrays and what the pieces of the loop share
+struct LoneRun {
+  rgpu_ctx* c;
+  int nsteps; double tEnd;
+  int* nStep; double* t; double* dt; double* dt_log;   // dt_log may be 0
+  const HistRun* hist;   // 0, or rgpu_run_steps_history
+  const MonRun* mon;     // 0, or rgpu_run_steps_monitored
+  int done = 0;          // steps of this call so far
+  int why = 0;           // 0, or the stop code of the record that ended the run (1: tEnd, 2: dt is not a number, 3: 1/dt is not finite --
+                         // the last two are also reported as RGPU_EHIP)
+};
+
+// the reference's loop body, with the head of MHDRunGodunov.cpp:3975-3984 in front of the step, literally, and the monitor of the
+// state the step left, U[*nStep % 2], behind it (one synchronisation per sample on this path)
+int literal_turn(LoneRun& run) {
+  rgpu_ctx* c = run.c;
+  const HistRun* H = run.hist;
+  if (H && hist_batch_due(*run.t, *run.dt, *H->tHist, H->dtHist)) {
+    double row[RGPU_HIST_NQ];
+    if (const int rc = rgpu_history_mri(c, *run.nStep % 2, row)) return rc;
+    H->put(*run.nStep, *run.t, *run.dt, row);
+    *H->tHist += H->dtHist;
+  }
+  if (const int rc = rgpu_one_step_integration(c, run.nStep, run.t, run.dt)) return rc;
+  if (run.dt_log) run.dt_log[run.done] = *run.dt;
+  ++run.done;
+  if (run.mon && run.mon->due(*run.nStep)) {
+    double v[RGPU_MON_NQ];
+    if (const int rc = state_monitor(c, c->g.three_d != 0, *run.nStep & 1, v)) return rc;
+    run.mon->put(*run.nStep, *run.t, v);
+  }
+  return RGPU_OK;
+}
+
+// what queueing a batch leaves for its harvest
+struct LoneBatch {
+  int queued = 0;                                // steps queued completely (their records are read back)
+  bool failed = false; std::string launch_err;   // a launch failed behind the `queued` steps, with this message
+};
+
+// Opens a batch and queues up to m steps: per step the tick, the history head of U[n % 2] (taken on the device if the record and the
+// log say so, kernels_history.h), the pieces of the step == rgpu_godunov_unsplit for this configuration, every dt / t dependence read
+// from the record on the device, and the monitor of U[(n + 1) % 2] behind the step's last kernel (taken if the record says that the
+// step ran).  != 0: the batch could not be opened, nothing was queued
+int batch_queue(LoneRun& run, int m, LoneBatch* b) {
+  rgpu_ctx* c = run.c;
+  const HistRun* H = run.hist;
+  const MonRun* M = run.mon;
+  // the logs of a batch: allocated by the first call that needs them
+  if (M && monitor_batch_alloc(c)) return RG_HIPFAIL(c, "run_steps_monitored: log of the batch");
+  if (H && !c->hist.allocated() && c->hist.alloc(rgpu_ctx::kClockBatch)) return RG_HIPFAIL(c, "run_steps_history: log of the batch");
+  if (const int rc = clock_open(c, *run.t, run.tEnd, true)) return rc;
+  const int n0 = *run.nStep;
+  const double dt0 = *run.dt;   // the loop's *dt at the head of the batch's first step
+  int rc = 0;
+  for (; b->queued < m; ++b->queued) {
+    if ((rc = rgpu_clock_tick(c)) != 0) break;
+    if (stop_now(c)) { ++b->queued; break; }   // (host emulation: the record is already there and says the loop has ended)
+    const int slot = b->queued, n = n0 + slot;
+    if (!clock_ready(c, n % 2)) rc = RGPU_EHIP;   // (cannot happen: the step before left its CFL maxima and, in 2D, its ghost cells)
+    if (rc == 0 && H && history_batch_queue(c, n, slot, dt0, *H->tHist, H->dtHist)) rc = RGPU_EHIP;
+    if (rc == 0) rc = (step_pre(c, n) || step_core(c, n, 0.0, 0.0) || step_post_a(c, n, 0.0, 0.0) || step_post_b(c, n)) ? RGPU_EHIP : 0;
+    if (rc == 0 && !c->rec.slots((n + 1) % 2)) rc = RGPU_EHIP;   // (cannot happen: same configuration, same kernels)
+    if (rc == 0 && M && M->due(n + 1) && monitor_batch_queue(c, (n + 1) & 1, slot)) rc = RGPU_EHIP;
+    if (rc) { c->clk_n = slot; break; }   // the record of the step that failed to queue is not read back
+  }
+  if (rc) { b->failed = true; b->launch_err = c->err + " " + rg_last_error_string(); }
+  return RGPU_OK;
+}
+
+// Reads back what the batch left and advances the run for the steps that ran.  A launch that failed after b.queued complete steps were
+// queued: those steps still run on the device -- their records are read and nStep / t / dt advanced for them before the failure is
+// reported, so that the caller's step count and parity describe the device state.  != 0: the code that ends the call
+int batch_harvest(LoneRun& run, const LoneBatch& b) {
+  rgpu_ctx* c = run.c;
+  const HistRun* H = run.hist;
+  const MonRun* M = run.mon;
+  const int queued = b.queued, n0 = *run.nStep;
+  // the logs travel with the clock records: queued behind them here, complete after the one synchronisation of rgpu_clock_close.  A
+  // history record behind the last head queued, a monitor slot no sample was queued for or whose step did not run: copied unwritten, not read
+  const bool log_ok = !H || queued == 0 || c->hist.download((size_t)queued, c->stream) == 0;
+  const bool mon_ok = !M || queued == 0 || c->mon.download((size_t)queued * RGPU_MON_NQ, c->stream) == 0;
+  const double t_open = *run.t;
+  int ran = 0, stop = 0;
+  if (const int rc = rgpu_clock_close(c, n0, &ran, run.t, run.dt, run.dt_log ? run.dt_log + run.done : 0, &stop)) return rc;
+  *run.nStep += ran;
+  run.done += ran;
+  if (M && ran > 0) {   // the host knows the step numbers; that step n0 + r ran is what the records said
+    if (!mon_ok) { c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps_monitored: read-back of the log"); }
+    double ta = t_open;
+    for (int r = 0; r < ran; ++r) {
+      ta += c->clk.h[r].dt;   // (*t as rgpu_clock_close accumulated it)
+      if (M->due(n0 + r + 1)) M->put(n0 + r + 1, ta, c->mon.h + (size_t)r * RGPU_MON_NQ);
+    }
+  }
+  if (H && ran > 0) {   // a step that ran had its head queued in front of it: records [0, ran) are written
+    if (!log_ok) { c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps_history: read-back of the log"); }
+    for (int r = 0; r < ran; ++r) {
+      const HistBatchRec& hr = c->hist.h[r];
+      if (hr.sampled) H->put(hr.step, hr.t, hr.dt, hr.v);
+    }
+    *H->tHist = c->hist.h[ran - 1].tHist;
+  }
+  if (b.failed) { c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps: queueing a device-clock step: " + b.launch_err); }
+  if (ran < queued) {
+    run.why = stop;
+    if (stop >= 2) return fail(c, RGPU_EHIP, stop_message(stop));
+  }
+  return RGPU_OK;
+}
+
+// the loop: per turn the literal body (the first step of a run always; a state without device maxima; consumers that cannot sample on
+// the device) or one batch.  Returns the steps done, or the code that ended the call -- *nStep, *t, *dt and the samples describe the
+// steps that ran either way
+int run_steps_impl(LoneRun& run) {
+  rgpu_ctx* c = run.c;
+  struct Current { rgpu_ctx* c; const int* n; ~Current() { c->cur = *n & 1; } } current = {c, run.nStep};   // however the loop is left: U[*nStep % 2] is the state
+  (void)current;
+  while (run.done < run.nsteps && *run.t < run.tEnd && !run.why) {
+    if (!clock_ready(c, *run.nStep % 2) || (run.hist && !run.hist->batch) || (run.mon && !monitor_scratch_fits(c))) {
+      if (const int rc = literal_turn(run)) return rc;
+      continue;
+    }
+    const int left = run.nsteps - run.done;
+    LoneBatch b;
+    if (const int rc = batch_queue(run, left < (int)rgpu_ctx::kClockBatch ? left : (int)rgpu_ctx::kClockBatch, &b)) return rc;
+    if (const int rc = batch_harvest(run, b)) return rc;
+  }
+  return run.done;
+}
+}  // namespace
+
+extern "C" {
+
+int rgpu_run_steps_log(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log) {
+  RG_CHECK_CTX(c);
+  if (!nStep || !t || !dt) return fail(c, RGPU_EINVAL, "run_steps: null pointer");
+  LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, 0};
+  return run_steps_impl(run);
+}
+
+int rgpu_run_steps(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt) {
+  return rgpu_run_steps_log(c, nsteps, tEnd, nStep, t, dt, 0);
+}
+
+long rgpu_history_batch_heads(rgpu_ctx* c) { return c ? c->hist_heads : 0; }
+
+int rgpu_run_steps_history(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, double dtHist, double* tHist,
+                           int* hist_n, int* hist_step, double* hist_t, double* hist_dt, double* hist) {
+  RG_CHECK_CTX(c);
+  if (!nStep || !t || !dt || !tHist || !hist_n || !hist_step || !hist_t || !hist_dt || !hist) return fail(c, RGPU_EINVAL, "run_steps_history: null pointer");
+  *hist_n = 0;
+  if (!c->U[0]) return fail(c, RGPU_EINVAL, "run_steps_history: context without state");
+  if (!c->p.mhdEnabled) return fail(c, RGPU_EUNSUPPORTED, "run_steps_history: history diagnostics are defined for MHD runs");
+  if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, "run_steps_history: slab contexts take their history through the slab driver");
+  if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_history: nsteps is negative");
+  const HistRun H = {dtHist, tHist, hist_n, hist_step, hist_t, hist_dt, hist, rgpu::options().history_batch != 0};
+  LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, &H, 0};
+  return run_steps_impl(run);
+}
+
+long rgpu_monitor_batch_samples(rgpu_ctx* c) { return c ? c->mon_samples : 0; }
+
+int rgpu_run_steps_monitored(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int every,
+                             int* mon_n, int* mon_step, double* mon_t, double* mon) {
+  RG_CHECK_CTX(c);
+  if (!nStep || !t || !dt || !mon_n || !mon_step || !mon_t || !mon) return fail(c, RGPU_EINVAL, "run_steps_monitored: null pointer");
+  *mon_n = 0;
+  if (!c->U[0]) return fail(c, RGPU_EINVAL, "run_steps_monitored: context without state");
+  if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, "run_steps_monitored: single-domain contexts only (a slab holds a part of the box)");
+  if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_monitored: nsteps is negative");
+  if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_monitored: every must be at least 1");
+  const MonRun M = {every, mon_n, mon_step, mon_t, mon};
+  LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
+  return run_steps_impl(run);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // kernels_history.h -- the device side of the MHD history diagnostics: per-thread bodies of the row / column sums, their flat functors
 // (rgpu_history_mri, rgpu_history_turbulence: api/history.h, api/entry_core.h), and the MRI row sampled INSIDE a batch of device-clock
-// steps (rgpu_run_steps_history, api/entry_clock.h).  Flat rg_launch functors throughout: any backend, the test-only host emulation
+// steps (rgpu_run_steps_history, api/run_steps.h).  Flat rg_launch functors throughout: any backend, the test-only host emulation
 // included.  The arithmetic behind the column sums is history_row.h, shared with the host and the slab driver.
 #pragma once
 #include "dev_numerics.h"

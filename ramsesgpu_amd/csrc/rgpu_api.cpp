@@ -29,5 +29,6 @@ using namespace rgpu_dev;
 #include "api/forcing.h"
 #include "api/entry_core.h"
 #include "api/entry_clock.h"
+#include "api/run_steps.h"
 #include "api/entry_ensemble.h"
 #include "api/entry_misc.h"

@@ -321,9 +321,9 @@ class Solver:
         n, t, d = C.c_int(self.nStep), C.c_double(self.totalTime), C.c_double(self.dt)
         log = (C.c_double * max(int(nsteps), 1))()
         done = self.lib.rgpu_run_steps_log(self.ctx, int(nsteps), float(tEnd), C.byref(n), C.byref(t), C.byref(d), log)
+        self.nStep, self.totalTime, self.dt = n.value, t.value, d.value   # (they describe the steps that ran, also when the call failed)
         if done < 0:
             self._chk(done, "run_steps")
-        self.nStep, self.totalTime, self.dt = n.value, t.value, d.value
         self.dt_log = [log[i] for i in range(done)]     # the time steps of this call, in order
         return done
 
@@ -340,9 +340,9 @@ class Solver:
         done = self.lib.rgpu_run_steps_history(self.ctx, int(nsteps), float(tEnd), C.byref(n), C.byref(t), C.byref(d), log, float(dtHist), C.byref(th), C.byref(hn),
                                                hstep.ctypes.data_as(C.POINTER(C.c_int)), ht.ctypes.data_as(_capi.c_double_p), hdt.ctypes.data_as(_capi.c_double_p),
                                                hv.ctypes.data_as(_capi.c_double_p))
+        self.nStep, self.totalTime, self.dt, self.tHist = n.value, t.value, d.value, th.value   # (also when the call failed)
         if done < 0:
             self._chk(done, "run_steps_history")
-        self.nStep, self.totalTime, self.dt, self.tHist = n.value, t.value, d.value, th.value
         self.dt_log = [log[i] for i in range(done)]
         k = hn.value
         return done, hstep[:k].copy(), ht[:k].copy(), hdt[:k].copy(), hv[:k].copy()

@@ -5,6 +5,7 @@
       with [history] enabled=yes did before; on this build and, with --baseline-lib, on ANOTHER build (the parent commit's), which is
       the column the acceptance of DESIGN 3.4.1 is phrased against
   (c) rgpu_run_steps without history on this build: what the cadence costs on top of the bare batches, (a) / (c)
+  --baseline-all: (a) and (c) on the other build as well, for a change that must leave every mode as fast as it was
 
     python scripts/history_bench.py [--baseline-lib OLD/librgpu_fast.so] [--out profiles/history_bench.json]
 
@@ -77,6 +78,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arith", default="contracted", choices=["exact", "contracted"])
     ap.add_argument("--baseline-lib", default=None, help="another build of the library (the parent commit's): mode (b) on it joins the alternation")
+    ap.add_argument("--baseline-all", action="store_true", help="modes (a) and (c) on the baseline library too (it must have them)")
+    ap.add_argument("--reverse", action="store_true", help="create the contexts of the modes in the opposite order")
     ap.add_argument("--workloads", default="mri-shipped,mri-128x256x128,orszag-tang-512,mri-512")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.7, help="seconds per timed window (well above 0.5)")
@@ -87,12 +90,13 @@ def main():
     rows = []
     for w in a.workloads.split(","):
         base, ov = WORKLOADS[w]
-        modes = {}
-        modes["a_run_steps_history"] = Run(lib, base, ov, "a")
-        modes["b_per_step"] = Run(lib, base, ov, "b")
+        makers = [("a_run_steps_history", lambda: Run(lib, base, ov, "a")), ("b_per_step", lambda: Run(lib, base, ov, "b"))]
         if base_lib:
-            modes["b_per_step_baseline"] = Run(base_lib, base, ov, "b")
-        modes["c_run_steps"] = Run(lib, base, ov, "c")
+            makers.append(("b_per_step_baseline", lambda: Run(base_lib, base, ov, "b")))
+        if base_lib and a.baseline_all:
+            makers += [("a_baseline", lambda: Run(base_lib, base, ov, "a")), ("c_baseline", lambda: Run(base_lib, base, ov, "c"))]
+        makers.append(("c_run_steps", lambda: Run(lib, base, ov, "c")))
+        modes = {name: make() for name, make in (makers[::-1] if a.reverse else makers)}
         steps = {name: calibrate(mode, a.window) for name, mode in modes.items()}
         rates, secs = {name: [] for name in modes}, {name: [] for name in modes}
         for _ in range(a.repeats):
@@ -103,7 +107,7 @@ def main():
                     dt = timed(mode, steps[name])
                 secs[name].append(dt)
                 rates[name].append(mode.cells * steps[name] / dt)
-        row = {"workload": w, "overrides": ov, "arithmetic": a.arith, "dtHist": "10 x the initial dt",
+        row = {"workload": w, "overrides": ov, "arithmetic": a.arith, "dtHist": "10 x the initial dt", "contexts_created": "reversed" if a.reverse else "as listed",
                "acceptance": "a_min_above_b_max: min of (a) above max of (b) on the baseline build (this build's (b) without --baseline-lib)",
                "what": "cell updates per second of the whole call, host clock around calls that end in a device synchronise"}
         for name, mode in modes.items():
@@ -115,6 +119,12 @@ def main():
             row["a_over_b"] = row["a_run_steps_history"]["median"] / ref["median"]
             row["a_min_above_b_max"] = row["a_run_steps_history"]["min"] > ref["max"]
             row["a_over_c"] = row["a_run_steps_history"]["median"] / row["c_run_steps"]["median"]
+        # no slower than the baseline's median by more than the baseline's own spread (max - min of its windows), mode by mode
+        for name, other in (("a_run_steps_history", "a_baseline"), ("b_per_step", "b_per_step_baseline"), ("c_run_steps", "c_baseline")):
+            if other in row:
+                o = row[other]
+                row[name + "_over_baseline"] = row[name]["median"] / o["median"]
+                row[name + "_holds"] = row[name]["median"] >= o["median"] - (o["max"] - o["min"])
         for mode in modes.values():
             mode.close()
         rows.append(row)

@@ -74,6 +74,19 @@ def test_samples_inside_the_device_batches(base, ov, every, lib):
     assert batch == len(steps) - (1 if every == 1 else 0) or (base, ov) == FOLDED
 
 
+BOUNDARY = [BATCHED[0], BATCHED[3], BATCHED[4]]
+
+
+@pytest.mark.parametrize("base,ov", BOUNDARY, ids=ids(BOUNDARY))
+def test_monitored_run_across_a_batch_boundary(base, ov, lib):
+    """300 steps, every 7th sampled: 7 does not divide the 256 steps of a batch, so which slots of a batch hold a sample differs between
+    the first batch and the second -- 3D hydro, the fused 2D MHD step, and the 2D hydro step with the folded clock, whose three slot
+    arrays rotate across the boundary"""
+    done, steps, vals, batch = m3.check_monitored_lone(lib, base, ov, 300, 7, expect_batch=batch_samples((base, ov), 7))
+    assert done == 300 and len(steps) == 42 and steps[-1] == 294
+    assert batch == 42 or (base, ov) == FOLDED
+
+
 @pytest.mark.parametrize("base,ov", m3.SEAMS, ids=ids(m3.SEAMS))
 def test_2d_shapes_at_the_seams_of_the_summation_order(base, ov, lib):
     """a 2D state is a volume of one plane (csrc/hip/monitor3d.h without its finish launch) at shapes where a lane, a round of the lanes

@@ -142,6 +142,17 @@ def test_monitored_run(base, ov, every, emu_lib):
         assert (batch > 0) == three_d   # the emulation runs the 3D device-clock batches; its 2D steps take their dt from the host
 
 
+BOUNDARY = [("implode3d", "mesh.nx=8;mesh.ny=8;mesh.nz=5"), ("mhd_mri_3d", "mesh.nx=8;mesh.ny=8;mesh.nz=8")]
+
+
+@pytest.mark.parametrize("base,ov", BOUNDARY, ids=ids(BOUNDARY))
+def test_monitored_run_across_a_batch_boundary(base, ov, emu_lib):
+    """300 steps, every 7th sampled: 7 does not divide the 256 steps of a batch, so which slots of a batch hold a sample differs between
+    the first batch and the second"""
+    done, steps, vals, batch = m3.check_monitored_lone(emu_lib, base, ov, 300, 7, expect_batch=batch_samples(7))
+    assert done == 300 and len(steps) == 42 and steps[-1] == 294 and batch == 42
+
+
 @pytest.mark.parametrize("base,ov", m3.SEAMS, ids=ids(m3.SEAMS))
 def test_2d_shapes_at_the_seams_of_the_summation_order(base, ov, emu_lib):
     """a 2D state is a volume of one plane: the flat functors at shapes where a lane, a round of the lanes or a segment begins or ends"""
