@@ -622,7 +622,10 @@ int rgpu_selftest_alfven(const rgpu_params* p, int n, const double* states36, do
 /* ---- Environment and options ------------------------------------------------------------------------------------------------
  * Environment variables the libraries read (all optional; everything else is an argument of an entry point):
  *   RGPU_TILED=0              librgpu.so: the flat per-cell kernels everywhere instead of the LDS-tiled cooperative ones (a second,
- *                             independently tested implementation of every step; 3-10x slower)
+ *                             independently tested implementation of every step; 3-10x slower).  On the device the default suite
+ *                             runs it in a child process, one case per step family against the oracle
+ *                             (tests/test_flat_path_gpu.py: test_flat_kernels_everywhere_vs_oracle); contexts with a per-cell gravity
+ *                             field take the same kernels in any process
  *   RGPU_COMM_SCHEDULE=1|2    librgpu_comm.so: step schedule of the slab driver where the caller leaves the choice to it (rgpu_comm_set_overlap(-1), rgpu_comm.h)
  *   RGPU_COMM_PACK=0          ... one send / recv per variable and face instead of the packed exchange
  *   RGPU_HALO_PRIO=high|low   ... priority of the halo stream (default: normal)

@@ -138,8 +138,9 @@ inline bool stop_now(const rgpu_ctx* c) { return RG_SYNC_LAUNCH && c->clk_cur &&
 struct Phase {
   rgpu_ctx* c; int which;
   Phase(rgpu_ctx* ctx, int w) : c(ctx), which(w) { if (c->timers_on && c->ev_ok) rg_event_record(c->ev0, c->stream); }
+  void drop() { which = -1; }   // nothing of this phase ran (a tiled kernel that does not cover the configuration): charge it no time
   ~Phase() {
-    if (c->timers_on && c->ev_ok) {
+    if (which >= 0 && c->timers_on && c->ev_ok) {
       rg_event_record(c->ev1, c->stream);
       c->t_acc[which] += rg_event_elapsed_ms(c->ev0, c->ev1) * 1e-3;
       c->t_calls[which] += 1;

@@ -168,6 +168,7 @@ int hydro_core(rgpu_ctx* c, const double* in, double* out, double dt_arg, int a,
     const int rc = rgpu_tiled::hydro3d_sweep(c->stream, g, in, out, dtdx, dtdy, dtdz, a, b, (scan || piece) ? c->d_red : 0, st.clk, a2, b2);
     if (rc == 0 && scan) c->rec.scanned(out_par, n3);
     if (rc <= 0) return rc;
+    ph.drop();               // not covered: no sweep ran, the phase timers must not say one did
     if (st.clk) return -1;   // the flat kernels take dt by value
     if (acc_piece) c->rec.disarm();   // flat kernels took over: no accumulated scan for this step
   }
@@ -184,6 +185,7 @@ int hydro_core(rgpu_ctx* c, const double* in, double* out, double dt_arg, int a,
     if (rc == 0 && n) c->rec.scanned(out_par, n);
     if (rc == 0 && images) c->rec.ghosts_written(out_par);
     if (rc <= 0) return rc;
+    ph.drop();               // not covered: the flat kernels below are the step
     if (st.clk) return -1;   // the flat kernels take dt by value
   }
   { Phase ph(c, RGPU_T_PRIM); K_hydro_prim<NV> k = {g, in, c->Q}; if (launch_planes<kBlock, 1>(c->stream, g, clip(a - 2, b + 2, ks), k)) return -1; }

@@ -538,8 +538,9 @@ def check_single_step_near_uniform(lib, oracle, base, ov, eps, seed=11, t0=0.0):
         sv.close()
 
 
-def check_run_vs_oracle(lib, oracle, base, ov, nsteps, exact=True):
-    """exact=False: the contracted-arithmetic variant of the library -- relative L2 < 1e-12 on the state, dt within 1e-11"""
+def check_run_vs_oracle(lib, oracle, base, ov, nsteps, exact=True, out=None):
+    """exact=False: the contracted-arithmetic variant of the library -- relative L2 < 1e-12 on the state, dt within 1e-11.
+    out: a dict that receives what the library returned ("state": the interior, "dts", "t"), before anything is compared"""
     p = lib.params_from_ini(ini(base), ov)
     U0 = lib.init_condition(ini(base), ov, p)
     attach_gravity(lib, base, ov, p, oracle=oracle)
@@ -548,6 +549,8 @@ def check_run_vs_oracle(lib, oracle, base, ov, nsteps, exact=True):
     try:
         attach_gravity(lib, base, ov, p, sv=sv)
         dts = sv.start(U0, nsteps)
+        if out is not None:
+            out.update(state=interior(sv.getDataHost(), p).copy(), dts=list(dts), t=sv.totalTime)
         if not exact:
             assert np.abs(np.array(dts) / np.asarray(dts_ref) - 1.0).max() < 1e-11, "%s: dt sequences differ beyond round-off" % base
             assert_same(interior(sv.getDataHost(), p), interior(ref, p), "%s [%s] %d steps vs oracle" % (base, ov, nsteps), exact=False)
@@ -638,9 +641,11 @@ BOUNDARY_CASES = [
 ]
 
 
-# The bench's launch geometry: planes of > 32768 cells, where the XCD-aware workgroup order splits each XCD's y band
-# into several sub-bands (rg_backend.h: rg_launch_planes, nsub > 1), with >= 2 chunks of the two-stream sweep and
-# the LDS-tiled kernels' full-width tile rows.  Few planes keep the oracle at seconds per step.
+# The bench's launch geometry: the LDS-tiled kernels' full-width tile rows, several rounds of workgroups and a sub-segmented last
+# round, on planes of > 32768 cells.  Few planes keep the oracle at seconds per step.  (These contexts run the tiled sweeps, which
+# neither read "xcd_sub" nor take the chunked two-stream schedule: the XCD-aware workgroup order of rg_launch_planes belongs to the
+# flat kernels' launch_planes calls and the chunk schedule to the flat 3D MHD kernels -- per-cell gravity field or RGPU_TILED=0 --
+# and both are pinned at this plane size by tests/test_flat_path_gpu.py.)
 BENCH_GEOMETRY = [
     ("mhd_mri_3d", "mesh.nx=512;mesh.ny=512;mesh.nz=16", 2),
     # the x-y cross-section of BASELINE config 5 (512 x 1024 x 512 over 8 GPUs): 33 x 129 tiles of the MHD sweep
@@ -654,15 +659,19 @@ def check_core_plane_pieces(lib, base, ov, state=None, oracle=None):
     """rgpu_step_core_planes over a partition of [0,ksize) (odd cuts, out of order) == rgpu_step_core; so is the split form
     (rgpu_step_core_planes_split: the fluxes of the whole box once, then the update piece by piece -- the slab driver's order).
     state: a stress_state family (STRESS_FAMILIES) instead of the initial condition; oracle: the whole call is also compared with the
-    oracle's step from the same state (dt equal, every double of the interior equal; the whole array on the rotating path)"""
+    oracle's step from the same state (dt equal, every double of the interior equal; the whole array on the rotating path).
+    A per-cell gravity field of the problem is attached (flat kernels: a piece of >= 16 planes takes the chunked two-stream schedule
+    of mhd3d_core from its own first plane)"""
     p = lib.params_from_ini(ini(base), ov)
     U0 = lib.init_condition(ini(base), ov, p) if state is None else stress_state(p, 3, state)
     ks = p.nz + 2 * p.ghostWidth
     cuts = [0, 1, 7, 8, ks - 15, ks]
     pieces = list(reversed(list(zip(cuts[:-1], cuts[1:]))))
     outs = []
+    attach_gravity(lib, base, ov, p, oracle=oracle)
     for mode in ("whole", "pieces", "split"):
         sv = Solver(p, lib)
+        attach_gravity(lib, base, ov, p, sv=sv)
         sv.upload(U0)
         sv.make_all_boundaries(0, 0.0, 0.0)
         dt = sv.compute_dt(0)

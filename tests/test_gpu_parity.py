@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import flat_path_checks as fp
 import parity_checks as pc
 from conftest import ROOT, golden_cases, ini
 from ramsesgpu_amd.solver import Solver, interior
@@ -84,12 +85,22 @@ def test_bench_launch_geometry_vs_oracle(base, ov, nsteps, gpu_lib, oracle):
 
 @pytest.mark.parametrize("sub", ["0", "2048", "4096"])
 @pytest.mark.parametrize("base,ov", [("mhd_mri_3d", "mesh.nx=224;mesh.ny=208;mesh.nz=16"),
-                                     ("implode3d", "mesh.nx=208;mesh.ny=224;mesh.nz=8;hydro.riemannSolver=hllc")],
-                         ids=["mri-224x208x16", "implode-208x224x8"])
+                                     ("implode3d", "mesh.nx=208;mesh.ny=224;mesh.nz=8;hydro.riemannSolver=hllc"),
+                                     ("mhd_mri_3d_stratified", "mesh.nx=224;mesh.ny=208;mesh.nz=16;hydro.slope_type=2.0;MRI.amp=0.3")],
+                         ids=["mri-224x208x16", "implode-208x224x8", "stratified-224x208x16"])
 def test_xcd_sub_band_sizes_vs_oracle(base, ov, sub, gpu_lib, oracle, monkeypatch):
-    """option "xcd_sub" (read at rgpu_create, kept per context): linear order, 2048- and 4096-cell sub-bands on a >= 200^2 plane"""
+    """option "xcd_sub" (read at rgpu_create, kept per context): linear order, 2048- and 4096-cell sub-bands on a >= 200^2 plane.
+    The option is read by the launch_planes calls of the FLAT kernels alone (api/step.h, api/forcing.h).  The stratified box has a
+    per-cell gravity field and runs them in any process: on it the option is exercised by default.  The first two cases run the tiled
+    sweeps, which never read it, unless the process runs under RGPU_TILED=0 -- tests/flat_worker.py runs exactly these two at these three
+    values in such a process, for tests/test_flat_path_gpu.py."""
     old = gpu_lib.set_option("xcd_sub", int(sub))
     try:
+        if base == "mhd_mri_3d_stratified":   # the model: band of 25 workgroups of 256, cut into 4 / 2 sub-bands with idle slots
+            p = gpu_lib.params_from_ini(ini(base), ov)
+            nsub = fp.box_facts(p, int(sub))["b256"]["nsub"]
+            assert p.gravityEnabled == 2 and nsub == {"0": None, "2048": 4, "4096": 2}[sub], nsub
+            oracle = fp.OnceOracle(oracle)     # one oracle run for the three values
         pc.check_run_vs_oracle(gpu_lib, oracle, base, ov, 2)
     finally:
         gpu_lib.set_option("xcd_sub", old)
@@ -137,7 +148,7 @@ def test_external_state_and_stream(gpu_lib):
 
 
 SLAB1 = [
-    ("mhd_mri_3d", "mesh.nx=32;mesh.ny=48;mesh.nz=40", 5),           # chunked two-stream sweep inside each plane range
+    ("mhd_mri_3d", "mesh.nx=32;mesh.ny=48;mesh.nz=40", 5),           # tiled sweep per plane range (under RGPU_TILED=0: the flat kernels' chunked two-stream schedule inside each range)
     ("orszag-tang3d", "mesh.nx=24;mesh.ny=24;mesh.nz=40", 4),
     ("orszag-tang3d", "mesh.nx=16;mesh.ny=16;mesh.nz=24;mesh.boundary_xmin=2;mesh.boundary_xmax=2;mesh.boundary_zmin=1;mesh.boundary_zmax=2", 4),
     ("implode3d", "mesh.nx=32;mesh.ny=32;mesh.nz=32;hydro.riemannSolver=hllc", 5),
@@ -166,8 +177,18 @@ def test_slab_schedule_world1(base, ov, nsteps, overlap, gpu_lib, oracle):
 
 
 @pytest.mark.parametrize("base,ov", [("mhd_mri_3d", "mesh.nx=16;mesh.ny=24;mesh.nz=44"),
-                                     ("implode3d", "mesh.nx=24;mesh.ny=24;mesh.nz=30")], ids=["mri", "implode3d"])
+                                     ("implode3d", "mesh.nx=24;mesh.ny=24;mesh.nz=30"),
+                                     ("mhd_mri_3d", "mesh.nx=40;mesh.ny=36;mesh.nz=40;gravity.static=yes")],
+                         ids=["mri", "implode3d", "mri-gravity-field"])
 def test_step_core_in_plane_pieces(base, ov, gpu_lib):
+    if "gravity.static=yes" in ov:
+        # per-cell gravity field: the flat 3D MHD kernels.  Of check_core_plane_pieces' pieces of ksize = 46, [8, 31) has 23 planes: the
+        # chunked two-stream schedule with C = 3 on a range that does not start at plane 0 (its first prim / elec / trace planes are
+        # clipped differently from the whole call's, which runs C = 5)
+        p = gpu_lib.params_from_ini(ini(base), ov)
+        ks = p.nz + 2 * p.ghostWidth
+        assert p.gravityEnabled == 2 and ks == 46
+        assert fp.chunk_facts(ks, gpu_lib.get_option("chunks"), (ks - 15) - 8)["C"] == 3 and fp.chunk_facts(ks, gpu_lib.get_option("chunks"), ks)["C"] == 5
     pc.check_core_plane_pieces(gpu_lib, base, ov)
 
 
@@ -268,9 +289,14 @@ OPTION_CASES_DISSIPATIVE = [("orszag-tang", "mesh.nx=40;mesh.ny=24;MHD.eta=0.02"
                             ("orszag-tang3d", "mesh.nx=24;mesh.ny=20;mesh.nz=16;hydro.nu=0.01;MHD.eta=0.02")]
 
 
-@pytest.mark.parametrize("option,value", [("ghost_images", 0), ("step_clock", 0), ("zseg", 5), ("spec", 0)])
-@pytest.mark.parametrize("base,ov", OPTION_CASES + OPTION_CASES_DISSIPATIVE,
-                         ids=[c[0] for c in OPTION_CASES] + [c[0] + "-dissipative" for c in OPTION_CASES_DISSIPATIVE])
+# ... and with a per-cell gravity field: the flat 3D MHD kernels, whose schedule "chunks" = 1 turns into the serial one (a list of its own again)
+OPTION_CASES_GRAVITY_FIELD = [("mhd_mri_3d", "mesh.nx=40;mesh.ny=36;mesh.nz=40;gravity.static=yes")]
+
+
+@pytest.mark.parametrize("option,value", [("ghost_images", 0), ("step_clock", 0), ("zseg", 5), ("spec", 0), ("chunks", 1)])
+@pytest.mark.parametrize("base,ov", OPTION_CASES + OPTION_CASES_DISSIPATIVE + OPTION_CASES_GRAVITY_FIELD,
+                         ids=[c[0] for c in OPTION_CASES] + [c[0] + "-dissipative" for c in OPTION_CASES_DISSIPATIVE]
+                         + [c[0] + "-gravity-field" for c in OPTION_CASES_GRAVITY_FIELD])
 def test_diagnostic_options_keep_the_bits(base, ov, option, value, gpu_lib):
     """every diagnostic option of the library (include/rgpu.h, "Environment and options") switches a fast path off or pins a launch
     plan: a batch of steps through rgpu_run_steps gives the same state and the same time steps either way"""
@@ -281,6 +307,7 @@ def test_diagnostic_options_keep_the_bits(base, ov, option, value, gpu_lib):
         old = gpu_lib.set_option(option, value) if on else None
         sv = Solver(p, gpu_lib)
         try:
+            pc.attach_gravity(gpu_lib, base, ov, p, sv=sv)
             sv.upload(U0, both=False); sv.make_all_boundaries(0, 0.0, 0.0); sv.upload(sv.getDataHost(0), both=True)
             assert sv.run_steps(7) == 7
             outs.append((interior(sv.getDataHost(), p).copy(), sv.totalTime, sv.dt))

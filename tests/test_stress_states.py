@@ -78,7 +78,9 @@ STRESS_OPTION_CASES = (
        ("spec", 0, "implode3d", "mesh.nx=33;mesh.ny=17;mesh.nz=30;hydro.riemannSolver=hllc;hydro.slope_type=2.0", "floor"),   # families
        ("spec", 0, "orszag-tang", "mesh.nx=46;mesh.ny=23", "floor"),
        ("spec", 0, "implode3d", "mesh.nx=33;mesh.ny=17;mesh.nz=1;hydro.riemannSolver=hllc", "floor"),
-       # XCD-ordered 2048-cell sub-bands on a >= 200^2 plane (MhLastX of the shearing box included)
+       # "xcd_sub" is read by the flat kernels' launch_planes calls alone: this context runs the tiled sweep (MhLastX of the shearing box
+       # included), which ignores it, unless the process runs under RGPU_TILED=0 -- then: XCD-ordered 2048-cell sub-bands on a >= 200^2
+       # plane.  The option on the device by default: tests/test_flat_path_gpu.py
        ("xcd_sub", 2048, "mhd_mri_3d", "mesh.nx=224;mesh.ny=208;mesh.nz=8", "contrast")])
 
 
