@@ -1,6 +1,6 @@
 // api/ctx.h -- the context of the C ABI (struct rgpu_ctx), parameter validation, allocation, creation.  Part of the ONE translation
-// unit rgpu_api.cpp (included there, in this order: ctx, boundaries, step, history, monitor, forcing, then the entry points: core,
-// clock, run_steps, ensemble, misc).
+// unit rgpu_api.cpp (included there, in this order: ctx, boundaries, step, step_hydro, step_mhd, step_core, history, monitor, forcing,
+// then the entry points: core, clock, run_steps, ensemble, misc).
 #pragma once
 // every entry point makes the context's device current: a multi-GPU process (or a thread whose current device differs)
 // would otherwise launch on the wrong device
@@ -73,7 +73,7 @@ struct rgpu_ctx {
   long t_calls[RGPU_T_COUNT] = {};
   rg_event_t ev0, ev1;
   bool ev_ok = false;
-  // z-chunked two-stream schedule of the 3D MHD step (mhd3d_core_overlap)
+  // z-chunked two-stream schedule of the flat 3D MHD step (mhd3d_chunked, api/step_mhd.h)
   enum { kMaxChunks = 256 };
   int nchunks = 1;
   rg_stream_t stream2 = (rg_stream_t)0;

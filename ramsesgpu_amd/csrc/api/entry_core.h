@@ -183,16 +183,7 @@ int rgpu_make_all_boundaries(rgpu_ctx* c, int parity, double totalTime, double d
   if (!c->U[0]) return fail(c, RGPU_EINVAL, "context was not created");
   boundary_call_invalidates_dt(c, parity, RGPU_XDIR, RGPU_ZDIR);
   Phase ph(c, RGPU_T_BOUNDARIES);
-  double* U = c->U[parity & 1];
-  int rc;
-  if (c->g.shearbox && c->g.three_d) {
-    rc = do_make_boundaries(c, U, RGPU_YDIR) || do_make_boundaries_shear(c, U, totalTime, dt) ||
-         do_make_boundaries(c, U, RGPU_ZDIR) || do_make_boundaries(c, U, RGPU_YDIR);
-  } else {
-    rc = do_make_boundaries(c, U, RGPU_XDIR) || do_make_boundaries(c, U, RGPU_YDIR) ||
-         (c->g.three_d && do_make_boundaries(c, U, RGPU_ZDIR));
-  }
-  if (rc) return RG_HIPFAIL(c, "make_all_boundaries");
+  if (fill_all_ghosts(c, c->U[parity & 1], totalTime, dt)) return RG_HIPFAIL(c, "make_all_boundaries");
   return RGPU_OK;
 }
 

@@ -54,7 +54,7 @@ int history_turbulence_columns(rgpu_ctx* c, int parity, double* h_cols) {
 // row of rgpu_history_mri of U[nStep % 2] when the loop's condition holds for this step, and write record `slot` of the log (c->hist) either way.
 // dt0, tHist0: the loop's *dt and *tHist at the head of the batch's first step (read by slot 0 only).
 // Scratch in F exactly as hist_scratch lays it out (the Reynolds column sums go where the vx sums were).  F is dead here: the
-// step before is complete in stream order (a batch is queued on the context stream alone: mhd3d_core is `serial` while c->clk_cur
+// step before is complete in stream order (a batch is queued on the context stream alone: mhd3d_core picks mhd3d_serial while c->clk_cur
 // is set, the fused 2D step is one launch), and the first kernel of the step that follows which touches F -- the 3D sweep
 // (rgpu_tiled::mhd3d_sweep) -- writes every entry of F, emf that the shear remap and the update read; step_pre's ghost fill works on
 // U alone and the fused 2D step does not use F at all.  It is the liveness rgpu_history_mri between two steps has always relied on.

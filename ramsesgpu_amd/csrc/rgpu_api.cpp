@@ -24,6 +24,9 @@ using namespace rgpu_dev;
 #include "api/ctx.h"
 #include "api/boundaries.h"
 #include "api/step.h"
+#include "api/step_hydro.h"
+#include "api/step_mhd.h"
+#include "api/step_core.h"
 #include "api/history.h"
 #include "api/monitor.h"
 #include "api/forcing.h"

@@ -7,7 +7,7 @@
 // the host's order (IEEE division, exact fmod; contraction off in both builds of the library), hence the same doubles:
 //   dt, dt/dx, dt/dy, dt/dz                                               rgpu_compute_dt, hydro_core / mhd3d_core
 //   rotating-frame coefficients lambda, ratio, alpha1, alpha2             rot_coef (MHDRunGodunov.cpp:2039-2053)
-//   shearing-box flux / emf remap offsets at t + dt/2                     mhd3d_core (MHDRunGodunov.cpp:3213-3216)
+//   shearing-box flux / emf remap offsets at t + dt/2                     shear_remap_at (MHDRunGodunov.cpp:3213-3216)
 //   shearing-box ghost remap offsets at t + dt                            do_make_boundaries_shear (MHDRunGodunov.cpp:3554-3557)
 // Shared by the HIP backend (hip/step_clock.h: the kernel) and the test-only host emulation (tests/emu/rg_tiled.h: a host loop),
 // and read by the step kernels through `const StepClock* clk` (0: the kernel takes its by-value arguments).

@@ -1,4 +1,4 @@
-"""The operator-split viscous / resistive stage (csrc/kernels_dissipative.h, launcher dissipative_nd in csrc/api/step.h) on rough states:
+"""The operator-split viscous / resistive stage (csrc/kernels_dissipative.h, launcher dissipative_nd in csrc/api/step_core.h) on rough states:
 checks shared by the CPU emulation tests (tests/test_dissipative_emu.py) and the GPU ones (tests/test_dissipative_gpu.py).
 
   ROUGH_RUNS    three steps from a random state on ONE context, the stage behind shapes that cross tile seams, use the MhLastX column,

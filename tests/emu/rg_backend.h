@@ -11,6 +11,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <typeinfo>
+#include <cxxabi.h>
 
 #define RG_DEVFN inline
 #define RG_BACKEND_NAME "host-emulation(test-only)"
@@ -25,7 +27,31 @@ using std::signbit;
 namespace rgpu {
 
 typedef int rg_stream_t;
-typedef double rg_event_t;
+struct rg_event_t { int id = -1; };   // id: given at create, so that the operation log can say which event a stream waits on
+
+// ---- log of device operations (off by default; rgpu_emu_oplog_* below): one line of text per operation, in issue order -- the kind,
+// for a launch the functor's type, the stream, idx0 and the count, for a memset or a copy the bytes, for an event its id and the stream.
+// No pointers: two runs of the same code give the same text.
+struct OpLog { bool on = false; int next_event = 0; std::string text; };
+inline OpLog& rg_oplog() { static OpLog l; return l; }
+template <class K>
+inline std::string rg_type_name() {
+  int st = 0;
+  char* d = abi::__cxa_demangle(typeid(K).name(), 0, 0, &st);
+  std::string s = (st == 0 && d) ? d : typeid(K).name();
+  std::free(d);
+  return s;
+}
+inline void rg_log_line(const std::string& line) { rg_oplog().text += line; rg_oplog().text += '\n'; }
+template <class K>
+inline void rg_log_launch(const char* kind, rg_stream_t s, unsigned long long idx0, unsigned long long n) {
+  if (!rg_oplog().on) return;
+  rg_log_line(std::string(kind) + " s=" + std::to_string(s) + " idx0=" + std::to_string(idx0) + " n=" + std::to_string(n) + " " + rg_type_name<K>());
+}
+inline void rg_log_op(const char* kind, rg_stream_t s, const char* key, unsigned long long v) {
+  if (!rg_oplog().on) return;
+  rg_log_line(std::string(kind) + " s=" + std::to_string(s) + " " + key + "=" + std::to_string(v));
+}
 
 // host stand-ins of the shared-reciprocal helpers: plain IEEE operations (the device versions return the same bits)
 struct rg_recip_t { double d; };
@@ -49,12 +75,14 @@ inline void rg_slot_max_wave(unsigned long long* slot, double v) { rg_slot_max(s
 enum { RG_DT_SLOTS = 1024 };
 
 template <int BLOCK, int MINW = 1, class K>
-inline int rg_launch(rg_stream_t, unsigned n, const K& k) {
+inline int rg_launch(rg_stream_t s, unsigned n, const K& k) {
+  rg_log_launch<K>("launch", s, 0, n);
   for (unsigned idx = 0; idx < n; ++idx) k(idx);
   return 0;
 }
 template <int BLOCK, int MINW = 1, class K>
-inline int rg_launch_range(rg_stream_t, unsigned idx0, unsigned n, const K& k) {
+inline int rg_launch_range(rg_stream_t s, unsigned idx0, unsigned n, const K& k) {
+  rg_log_launch<K>("launch_range", s, idx0, n);
   for (unsigned off = 0; off < n; ++off) k(idx0 + off);
   return 0;
 }
@@ -62,13 +90,15 @@ inline int rg_launch_range(rg_stream_t, unsigned idx0, unsigned n, const K& k) {
 // once, like a launch error would; 0 = disarmed.  Armed through rgpu_emu_fail_launch_after() below.
 inline int& rg_fail_countdown() { static int n = 0; return n; }
 template <int BLOCK, int MINW = 1, class K>
-inline int rg_launch_planes(rg_stream_t, unsigned idx0, unsigned plane_cells, unsigned nplanes, const K& k, unsigned = 0) {
+inline int rg_launch_planes(rg_stream_t s, unsigned idx0, unsigned plane_cells, unsigned nplanes, const K& k, unsigned = 0) {
   if (rg_fail_countdown() > 0 && --rg_fail_countdown() == 0) return -1;
+  rg_log_launch<K>("launch_planes", s, idx0, (unsigned long long)plane_cells * nplanes);
   for (unsigned off = 0; off < plane_cells * nplanes; ++off) k(idx0 + off);
   return 0;
 }
 template <class K>
-inline int rg_reduce_max(rg_stream_t, unsigned n, const K& k, unsigned long long* out, unsigned idx0 = 0, bool reset = true) {
+inline int rg_reduce_max(rg_stream_t s, unsigned n, const K& k, unsigned long long* out, unsigned idx0 = 0, bool reset = true) {
+  rg_log_launch<K>("reduce", s, idx0, n);
   double v = 0.0;
   if (!reset) std::memcpy(&v, out, sizeof(double));
   for (unsigned off = 0; off < n; ++off) v = std::fmax(v, k(idx0 + off));
@@ -83,24 +113,31 @@ inline int rg_malloc(void** p, size_t bytes) { *p = std::malloc(bytes ? bytes : 
 inline void rg_free(void* p) { std::free(p); }
 inline int rg_host_alloc(void** p, size_t bytes) { return rg_malloc(p, bytes); }
 inline void rg_host_free(void* p) { std::free(p); }
-inline int rg_memset_async(void* p, int v, size_t bytes, rg_stream_t) { std::memset(p, v, bytes); return 0; }
-inline int rg_copy_h2d(void* d, const void* h, size_t bytes, rg_stream_t) { std::memcpy(d, h, bytes); return 0; }
-inline int rg_copy_d2h(void* h, const void* d, size_t bytes, rg_stream_t) { std::memcpy(h, d, bytes); return 0; }
-inline int rg_copy_d2d(void* d, const void* s_, size_t bytes, rg_stream_t) { std::memcpy(d, s_, bytes); return 0; }
+inline int rg_memset_async(void* p, int v, size_t bytes, rg_stream_t s) { rg_log_op("memset", s, "bytes", bytes); std::memset(p, v, bytes); return 0; }
+inline int rg_copy_h2d(void* d, const void* h, size_t bytes, rg_stream_t s) { rg_log_op("copy_h2d", s, "bytes", bytes); std::memcpy(d, h, bytes); return 0; }
+inline int rg_copy_d2h(void* h, const void* d, size_t bytes, rg_stream_t s) { rg_log_op("copy_d2h", s, "bytes", bytes); std::memcpy(h, d, bytes); return 0; }
+inline int rg_copy_d2d(void* d, const void* s_, size_t bytes, rg_stream_t s) { rg_log_op("copy_d2d", s, "bytes", bytes); std::memcpy(d, s_, bytes); return 0; }
 inline rg_stream_t rg_stream_from_handle(void*) { return 0; }
 inline void* rg_stream_to_handle(rg_stream_t) { return 0; }
 inline int rg_stream_sync(rg_stream_t) { return 0; }
 inline const char* rg_last_error_string() { return "emulation"; }
 inline int rg_stream_create(rg_stream_t* s, int = 0) { *s = 1; return 0; }
 inline void rg_stream_destroy(rg_stream_t) {}
-inline int rg_order_event_create(rg_event_t* e) { *e = 0; return 0; }
-inline int rg_stream_wait_event(rg_stream_t, rg_event_t) { return 0; }
-inline int rg_event_create(rg_event_t* e) { *e = 0; return 0; }
+inline int rg_event_create(rg_event_t* e) { e->id = rg_oplog().next_event++; return 0; }
+inline int rg_order_event_create(rg_event_t* e) { return rg_event_create(e); }
+inline int rg_stream_wait_event(rg_stream_t s, rg_event_t e) { rg_log_op("wait", s, "event", (unsigned long long)e.id); return 0; }
 inline void rg_event_destroy(rg_event_t) {}
-inline int rg_event_record(rg_event_t, rg_stream_t) { return 0; }
+inline int rg_event_record(rg_event_t e, rg_stream_t s) { rg_log_op("record", s, "event", (unsigned long long)e.id); return 0; }
 inline double rg_event_elapsed_ms(rg_event_t, rg_event_t) { return 0.0; }
 
 }  // namespace rgpu
 
-// TEST-ONLY entry point of the emulation library (single translation unit: defined here)
+// TEST-ONLY entry points of the emulation library (single translation unit: defined here)
 extern "C" inline __attribute__((used, visibility("default"))) void rgpu_emu_fail_launch_after(int n) { rgpu::rg_fail_countdown() = n; }
+// the operation log: on != 0 empties the log, numbers the events created from now on from 0 and starts logging; 0 stops (the text stays)
+extern "C" inline __attribute__((used, visibility("default"))) void rgpu_emu_oplog_enable(int on) {
+  rgpu::OpLog& l = rgpu::rg_oplog();
+  l.on = on != 0;
+  if (on) { l.text.clear(); l.next_event = 0; }
+}
+extern "C" inline __attribute__((used, visibility("default"))) const char* rgpu_emu_oplog_text() { return rgpu::rg_oplog().text.c_str(); }

@@ -2,10 +2,10 @@
 kernels_mhd3d.h) on the device, at shapes where the two pieces of launch machinery that belong to them alone engage --
 
   * the XCD-aware workgroup order of rg_launch_planes / rg_kernel_planes (csrc/hip/rg_backend.h), which every launch_planes call of
-    api/step.h and api/forcing.h goes through: the flat hydro kernels (2D: one plane), the flat 3D MHD prim / elec / trace / Riemann
+    api/step_hydro.h, api/step_mhd.h and api/forcing.h goes through: the flat hydro kernels (2D: one plane), the flat 3D MHD prim / elec / trace / Riemann
     kernels, rgpu_add_forcing and the Ornstein-Uhlenbeck kick.  (The flat 2D MHD kernels and the 3D MHD update are launched over a
     linear index range and never read "xcd_sub".)
-  * the chunked two-stream schedule of mhd3d_core (api/step.h): flat 3D MHD only.
+  * the chunked two-stream schedule mhd3d_chunked (api/step_mhd.h): flat 3D MHD only.
 
 A context takes the flat kernels when it has a per-cell gravity field (grav_on == 2) or when the process runs under RGPU_TILED=0.
 
@@ -90,7 +90,7 @@ def cover_counts(workgroups, ncells):
 
 
 def chunk_facts(ksize, chunks_option, span, timers=False):
-    """rgpu_create's nchunks (api/ctx.h) and mhd3d_core's schedule (api/step.h) for a flat 3D MHD update of `span` planes with what == 0
+    """rgpu_create's nchunks (api/ctx.h) and mhd3d_core's choice of schedule (api/step_mhd.h: mhd3d_serial / mhd3d_chunked) for a flat 3D MHD update of `span` planes with what == 0
     and no device clock: {"nchunks", "serial", "C" (chunks of the two-stream schedule; 1 when serial), "cuts" (the chunk ends, relative
     to the first plane)}.  chunks_option: the option "chunks" (<= 0: the default, ksize / 8)"""
     want = chunks_option if chunks_option > 0 else ksize // 8
@@ -227,7 +227,7 @@ def check_forcing_probe(lib, base, ov, sub_option, want):
 # ---- C. which path a configuration takes, and runs against an oracle that is asked once ----------------------------------------------
 def assert_flat_path(lib, base, ov):
     """one timed step on a context of its own: the phase timers say which kernels ran -- the flat prim / trace / flux kernels (and elec
-    for 3D MHD), no tiled sweep.  (Timers force the serial schedule of mhd3d_core: the compared runs are untimed.)"""
+    for 3D MHD), no tiled sweep.  (Timers make mhd3d_core pick the serial schedule: the compared runs are untimed.)"""
     p = lib.params_from_ini(ini(base), ov)
     U0 = lib.init_condition(ini(base), ov, p)
     sv = Solver(p, lib)

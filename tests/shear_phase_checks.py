@@ -3,8 +3,8 @@ and the GPU ones (tests/test_shear_phase_gpu.py).
 
 Each step of the rotating shearing box consumes two time-dependent row offsets, both from
     deltay = fmod(1.5 Omega0 xlen t, ylen),  jplus = (int)(deltay / dy),  eps = fmod(deltay, dy) / dy
--- the flux / emf remap at t + dt/2 and the x-ghost remap at t + dt -- and that arithmetic is written out on the host (api/step.h,
-api/boundaries.h twice), on the device (step_clock_rec.h: step_clock_form, read by the kernels of a device-clock batch) and in the slab
+-- the flux / emf remap at t + dt/2 and the x-ghost remap at t + dt -- and that arithmetic is written out on the host (api/step_mhd.h:
+shear_remap_at; api/boundaries.h twice), on the device (step_clock_rec.h: step_clock_form, read by the kernels of a device-clock batch) and in the slab
 driver's clock; the consumers index rows with a periodic wrap.  An off-by-one row, a wrong wrap or a device / host fmod mismatch shows
 only where jplus is near ny - 1, where the fmod(., ylen) wrap falls between t + dt/2 and t + dt, or where a batch starts at t != 0.
 So the runs here are PLANTED: t0 is chosen from the oracle's own dt sequence so that the K steps have a named property (PLANTS), the

@@ -1,4 +1,4 @@
-"""The viscous / resistive stage (csrc/kernels_dissipative.h, dissipative_nd in csrc/api/step.h) on the GPU, both libraries, on rough states
+"""The viscous / resistive stage (csrc/kernels_dissipative.h, dissipative_nd in csrc/api/step_core.h) on the GPU, both libraries, on rough states
 (tests/dissipative_checks.py; CPU twin: tests/test_dissipative_emu.py).
 
   three steps on one context   random state (seed 5, Mach 1), the stage behind the tile shapes of tests/test_stress_states.py; with the

@@ -69,7 +69,7 @@ def test_plane_map_model_on_the_shapes_of_this_module():
     f, g = fp.plane_map_facts(234 * 154, 256, 4096), fp.plane_map_facts(234 * 154, 64, 4096)      # Keplerian disk 230 x 150, one plane
     assert (f["nsub"], g["nsub"], f["in_band_guard_live"], g["in_band_guard_live"]) == (2, 2, False, True), (f, g)
     assert fp.plane_map_facts(46 * 30, 256, 4096)["reordered"] is False      # the largest flat plane of the suite before this module
-    # the chunk schedule: rgpu_create's clamps and mhd3d_core's C
+    # the chunk schedule: rgpu_create's clamps and mhd3d_chunked's C
     assert fp.chunk_facts(46, -1, 46) == {"nchunks": 5, "serial": False, "C": 5, "cuts": [9, 18, 27, 36, 46]}
     assert fp.chunk_facts(46, 40, 46)["nchunks"] == 23 and fp.chunk_facts(46, 40, 46)["C"] == 6          # both clamps act
     assert fp.chunk_facts(46, 1, 46)["serial"] and fp.chunk_facts(46, -1, 46, timers=True)["serial"] and fp.chunk_facts(46, -1, 15)["serial"]

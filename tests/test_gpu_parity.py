@@ -90,7 +90,7 @@ def test_bench_launch_geometry_vs_oracle(base, ov, nsteps, gpu_lib, oracle):
                          ids=["mri-224x208x16", "implode-208x224x8", "stratified-224x208x16"])
 def test_xcd_sub_band_sizes_vs_oracle(base, ov, sub, gpu_lib, oracle, monkeypatch):
     """option "xcd_sub" (read at rgpu_create, kept per context): linear order, 2048- and 4096-cell sub-bands on a >= 200^2 plane.
-    The option is read by the launch_planes calls of the FLAT kernels alone (api/step.h, api/forcing.h).  The stratified box has a
+    The option is read by the launch_planes calls of the FLAT kernels alone (api/step_hydro.h, api/step_mhd.h, api/forcing.h).  The stratified box has a
     per-cell gravity field and runs them in any process: on it the option is exercised by default.  The first two cases run the tiled
     sweeps, which never read it, unless the process runs under RGPU_TILED=0 -- tests/flat_worker.py runs exactly these two at these three
     values in such a process, for tests/test_flat_path_gpu.py."""
