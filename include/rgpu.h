@@ -601,6 +601,64 @@ int rgpu_run_steps_monitored(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, d
                              int every, int* mon_n, int* mon_step /* [cap] */, double* mon_t /* [cap] */, double* mon /* [cap][RGPU_MON_NQ] */);
 long rgpu_monitor_batch_samples(rgpu_ctx* c);
 
+/* ---- plane monitors: z profiles of a 3D state, reduced on the device ----------------------------------------------------------------
+ * What a 3D run is plotted from is resolved along z: the space-time diagram of the mean By(z, t) of an MRI box, the profiles of the
+ * Maxwell and Reynolds stresses, the density profile of a stratified box, <rho>(z) and <rho^2>(z) of a mixing layer.  A plane monitor
+ * is RGPU_MONP_NQ = 16 doubles for EVERY interior plane kk = k - ghostWidth in [0, nz) of U[parity] of a single-domain 3D context,
+ * hydro or MHD, shearing box included, taken over the nx x ny interior cells of the plane and raw (not multiplied by dx dy):
+ *     q  0 .. 9   the ten columns of the 3D monitor above (seven sums, min_rho, min_eint, max_absdivb), from the same per-cell terms
+ *       10 bx   11 by   12 bz   13 bxby   14 rvxvy   15 rho2                                     sums
+ * Terms of cell (i, j, k) of columns 10 - 15, IEEE + - * / in exactly this order, no FMA contraction in either library
+ * (csrc/kernels_monitor_planes.h), with rho, mx, my, bxc, byc, bzc as defined for the 3D monitor:
+ *     MHD:   bx = bxc, by = byc, bz = bzc (the cell-centred field), bxby = bxc * byc
+ *     hydro: bx = by = bz = bxby = +0.0              (columns 6, 9 and 10 - 13 of a hydro state are exactly +0.0)
+ *     rvxvy = (mx * my) / rho,   rho2 = rho * rho
+ * Row kk: steps 1 - 4 of the summation order above (segments of RGPU_MON_ROWS rows, columns, RGPU_MON_LANES lanes, butterfly) applied
+ * to the nx x ny cells of plane kk; columns 7, 8 and 9 take fmin / fmin / fmax along the same route.  There is no step 5 and there are
+ * no floating-point atomics: a row depends on (nx, ny) and on its own plane only -- not on nz, the library, the position in a batch,
+ * or how the kernels cut the grid.  No ghost fill is done; the high faces of the last interior row, column and plane come from the
+ * first ghost layer, as for the monitors.  The NaN rules are the monitors', per plane: a NaN cell propagates into the sums of its
+ * own plane that contain it, drops out of that plane's extrema, and changes no other row.
+ * Identity: folding the rows ascending in kk from (+0.0 for the sums, +inf for the minima, +0.0 for the maximum) with + / fmin / fmax
+ * gives, in columns 0 - 9, the ten doubles of rgpu_state_monitor3d on that state, bit for bit (row kk is V[kk] of its order).
+ * (tests/monitor_planes_checks.py is this definition in numpy.)
+ *
+ *   rgpu_state_monitor_planes   out[nz][RGPU_MONP_NQ] of U[parity].  Reads the state only: ghost cells, CFL slots and what the context
+ *                          knows about them stay as they are.  Synchronises.  2D context: RGPU_EUNSUPPORTED ("3D" in the message);
+ *                          slab context (slab_count > 1): RGPU_EINVAL; NULL pointer: RGPU_EINVAL; partial sums that do not fit the
+ *                          flux array: RGPU_EINVAL.
+ *   rgpu_run_steps_monitored_planes   rgpu_run_steps_log (same states, same dt sequence, same return value) plus sampling, with the
+ *                          semantics of rgpu_run_steps_monitored word for word: a sample after each step that brings *nStep to a
+ *                          multiple of `every`; *mon_n = the samples of this call (<= cap = nsteps / every + 1); sample k: mon_step[k],
+ *                          mon_t[k] the host-accumulated *t after that step, mon[(k * nz + kk) * RGPU_MONP_NQ + q] the rows of
+ *                          rgpu_state_monitor_planes on that state, bit for bit.  A step that reaches tEnd is sampled if it qualifies,
+ *                          nothing is sampled after a stop; *mon_n counts only samples whose values were written.  A run cut into
+ *                          calls gives the series of one call.  dt_log may be NULL.
+ *                          Where the context takes its time step from the device (rgpu_device_time_step_ready) the two kernels of a
+ *                          sample (csrc/hip/monitor_profile.h) are queued behind the last kernel of each qualifying step, return in
+ *                          their first instructions when the step's clock record says stop, and write to a device log that is copied
+ *                          back once per batch with the clock records: no synchronisation inside a batch.  Everywhere else (first
+ *                          steps, gravity, the dissipative stage, forcing, phase timers, option "step_clock" = 0) the call is the
+ *                          literal loop: rgpu_one_step_integration, then rgpu_state_monitor_planes.  A call samples the monitor or
+ *                          the planes, not both: the monitor's columns are the fold of the rows (the identity above).
+ *                          Memory: the partial sums (RGPU_MONP_NQ x nz x ceil(ny / RGPU_MON_ROWS) x nx doubles, then the nz rows of
+ *                          a sample taken outside a batch) go to the flux array, dead between steps.  The log -- RGPU_CLOCK_BATCH /
+ *                          every + 1 slots of nz x RGPU_MONP_NQ doubles, the samples that can fall into one batch -- and its pinned
+ *                          mirror of the same size are allocated by the first call that needs them, grown if a later call needs
+ *                          more, freed with the context, and are not part of rgpu_device_bytes.
+ *                          Errors: RGPU_EUNSUPPORTED for a 2D context; RGPU_EINVAL for every < 1 ("every" in the message), a NULL
+ *                          pointer among nStep, t, dt, mon_n, mon_step, mon_t, mon, nsteps < 0, a slab context, or partial sums that
+ *                          do not fit the flux array.
+ *   rgpu_monitor_planes_batch_samples   how many plane samples this context has queued on the device inside its batches so far (0
+ *                          where every call took the literal loop), as rgpu_monitor_batch_samples -- which these calls leave alone. */
+#define RGPU_MONP_NQ 16
+#define RGPU_MONP_NAMES "mass mx my mz E ekin emag min_rho min_eint max_absdivb bx by bz bxby rvxvy rho2"   /* the RGPU_MONP_NQ columns, in order */
+int rgpu_state_monitor_planes(rgpu_ctx* c, int parity, double* out /* [nz][RGPU_MONP_NQ] */);
+int rgpu_run_steps_monitored_planes(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log,
+                                    int every, int* mon_n, int* mon_step /* [cap] */, double* mon_t /* [cap] */,
+                                    double* mon /* [cap][nz][RGPU_MONP_NQ] */);
+long rgpu_monitor_planes_batch_samples(rgpu_ctx* c);
+
 /* Self-test of the device arithmetic the parity contract rests on: for n operand pairs computes on the device
  *   quot[i]  = rg_div(num[i], rg_recip(den[i]))   the shared-reciprocal division of csrc/hip/rg_backend.h
  *   quot2[i] = num[i] / den[i]                    the compiler's IEEE division

@@ -10,6 +10,9 @@ XDIR, YDIR, ZDIR = 1, 2, 3
 # the columns of a monitor (rgpu_state_monitor, rgpu_ensemble_monitor, rgpu_ensemble_run_steps_monitored): RGPU_MON_NQ = 10
 MON_NAMES = ("mass", "mx", "my", "mz", "E", "ekin", "emag", "min_rho", "min_eint", "max_absdivb")
 MON_NQ = len(MON_NAMES)
+# the columns of a row of the plane monitor (rgpu_state_monitor_planes, rgpu_run_steps_monitored_planes): RGPU_MONP_NQ = 16
+MONP_NAMES = MON_NAMES + ("bx", "by", "bz", "bxby", "rvxvy", "rho2")
+MONP_NQ = len(MONP_NAMES)
 T_NAMES = ["boundaries", "prim", "elec", "trace", "flux", "emf", "update", "shear", "dt", "dissipative", "sweep"]
 
 
@@ -219,6 +222,14 @@ def declare_device_api(lib):
                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]
         lib.rgpu_monitor_batch_samples.restype = C.c_long
         lib.rgpu_monitor_batch_samples.argtypes = [ctx]
+    if hasattr(lib, "rgpu_state_monitor_planes"):   # (absent from an older build of the library: scripts/monitor_planes_bench.py --baseline-lib)
+        lib.rgpu_state_monitor_planes.restype = C.c_int
+        lib.rgpu_state_monitor_planes.argtypes = [ctx, C.c_int, c_double_p]
+        lib.rgpu_run_steps_monitored_planes.restype = C.c_int
+        lib.rgpu_run_steps_monitored_planes.argtypes = [ctx, C.c_int, C.c_double, C.POINTER(C.c_int), c_double_p, c_double_p, c_double_p, C.c_int,
+                                                        C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]
+        lib.rgpu_monitor_planes_batch_samples.restype = C.c_long
+        lib.rgpu_monitor_planes_batch_samples.argtypes = [ctx]
     return lib
 
 
@@ -269,4 +280,5 @@ DECLARED_SYMBOLS = [
     "rgpu_ensemble_create_scan", "rgpu_ensemble_scan_device_bytes",
     "rgpu_state_monitor", "rgpu_ensemble_monitor", "rgpu_ensemble_run_steps_monitored", "rgpu_ensemble_monitor_device_bytes",
     "rgpu_state_monitor3d", "rgpu_run_steps_monitored", "rgpu_monitor_batch_samples",
+    "rgpu_state_monitor_planes", "rgpu_run_steps_monitored_planes", "rgpu_monitor_planes_batch_samples",
 ]

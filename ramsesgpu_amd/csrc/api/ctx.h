@@ -97,6 +97,12 @@ struct rgpu_ctx {
   // allocated by the first call that needs them
   DeviceMirror<double> mon;
   long mon_samples = 0;         // monitor samples queued on the device so far (rgpu_monitor_batch_samples)
+  // the plane-monitor samples taken inside a batch (kernels_monitor_planes.h; rgpu_run_steps_monitored_planes): monp_slots slots of
+  // nz x MONP_NQ doubles, as many as the cadence of the call lets fall into one batch; allocated by the first call that needs them,
+  // grown by a later one that needs more
+  DeviceMirror<double> monp;
+  size_t monp_slots = 0;
+  long monp_samples = 0;        // plane-monitor samples queued on the device so far (rgpu_monitor_planes_batch_samples)
   // fused 2D steps: the clock is folded into the step kernel itself (step_clock_rec.h: ClockFold) over three rotating slot arrays;
   // d_red always points at the array that holds the maxima of the current state
   unsigned long long* d_red_base = 0;   // 3 x RG_DT_SLOTS

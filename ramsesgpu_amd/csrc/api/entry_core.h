@@ -308,6 +308,7 @@ int rgpu_state_checksum(rgpu_ctx* c, int parity, unsigned long long* out) {
 
 int rgpu_state_monitor(rgpu_ctx* c, int parity, double* out) { return state_monitor(c, false, parity, out); }
 int rgpu_state_monitor3d(rgpu_ctx* c, int parity, double* out) { return state_monitor(c, true, parity, out); }
+int rgpu_state_monitor_planes(rgpu_ctx* c, int parity, double* out) { return state_monitor_planes(c, parity, out); }
 
 double rgpu_compute_dt(rgpu_ctx* c, int useU) {
   double v = 0;

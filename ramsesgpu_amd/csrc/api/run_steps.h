@@ -1,4 +1,4 @@
-// api/run_steps.h -- entry points: the time loop of a lone context (rgpu_run_steps, _log, _history, _monitored; every member-alone round
+// api/run_steps.h -- entry points: the time loop of a lone context (rgpu_run_steps, _log, _history, _monitored, _monitored_planes; every member-alone round
 // of an ensemble comes through here too).  One LoneRun per call; per turn either the reference's loop body (literal_turn) or a batch
 // of device-clock steps (api/entry_clock.h), queued by batch_queue and read back once by batch_harvest.  The two optional consumers
 // of a step -- the history row in front of it, the monitor sample behind it -- each write the caller's arrays in one place, put().
@@ -18,15 +18,18 @@ struct HistRun {
 };
 static_assert((int)HIST_BATCH_NQ == RGPU_HIST_NQ, "include/rgpu.h states the width of a history row");
 
-// what rgpu_run_steps_monitored adds to the loop: the cadence in steps and where the samples go (see include/rgpu.h)
+// what rgpu_run_steps_monitored and rgpu_run_steps_monitored_planes add to the loop: the cadence in steps, which of the two samples
+// is taken -- the monitor's RGPU_MON_NQ doubles, or (planes) the plane monitor's nz x RGPU_MONP_NQ -- and where the samples go (see
+// include/rgpu.h).  One consumer, two samples: api/monitor.h chooses the launches by `planes`
 struct MonRun {
-  int every;
-  int* n; int* step; double* t; double* v;   // *n samples so far; step[k], t[k], v[k][RGPU_MON_NQ]
+  int every; bool planes; size_t width;      // width: the doubles of a sample
+  int* n; int* step; double* t; double* v;   // *n samples so far; step[k], t[k], v[k][width]
+  const char* who;                           // the entry point, for messages
   bool due(int step_no) const { return step_no % every == 0; }   // the state step number step_no names is sampled
-  void put(int step_no, double ts, const double* values) const {
+  double* slot() const { return v + (size_t)*n * width; }        // where the values of the next sample go
+  void put(int step_no, double ts) const {                        // the values are in slot()
     const int k = (*n)++;
     step[k] = step_no; t[k] = ts;
-    std::memcpy(v + (size_t)k * RGPU_MON_NQ, values, RGPU_MON_NQ * sizeof(double));
   }
 };
 
@@ -57,9 +60,9 @@ int literal_turn(LoneRun& run) {
   if (run.dt_log) run.dt_log[run.done] = *run.dt;
   ++run.done;
   if (run.mon && run.mon->due(*run.nStep)) {
-    double v[RGPU_MON_NQ];
-    if (const int rc = state_monitor(c, c->g.three_d != 0, *run.nStep & 1, v)) return rc;
-    run.mon->put(*run.nStep, *run.t, v);
+    const MonRun* M = run.mon;
+    if (const int rc = M->planes ? state_monitor_planes(c, *run.nStep & 1, M->slot()) : state_monitor(c, c->g.three_d != 0, *run.nStep & 1, M->slot())) return rc;
+    M->put(*run.nStep, *run.t);
   }
   return RGPU_OK;
 }
@@ -67,6 +70,7 @@ int literal_turn(LoneRun& run) {
 // what queueing a batch leaves for its harvest
 struct LoneBatch {
   int queued = 0;                                // steps queued completely (their records are read back)
+  int samples = 0;                               // monitor samples queued behind them: slots [0, samples) of the log, in step order
   bool failed = false; std::string launch_err;   // a launch failed behind the `queued` steps, with this message
 };
 
@@ -79,7 +83,7 @@ int batch_queue(LoneRun& run, int m, LoneBatch* b) {
   const HistRun* H = run.hist;
   const MonRun* M = run.mon;
   // the logs of a batch: allocated by the first call that needs them
-  if (M && monitor_batch_alloc(c)) return RG_HIPFAIL(c, "run_steps_monitored: log of the batch");
+  if (M && monitor_batch_alloc(c, M->planes, M->every)) return RG_HIPFAIL(c, std::string(M->who) + ": log of the batch");
   if (H && !c->hist.allocated() && c->hist.alloc(rgpu_ctx::kClockBatch)) return RG_HIPFAIL(c, "run_steps_history: log of the batch");
   if (const int rc = clock_open(c, *run.t, run.tEnd, true)) return rc;
   const int n0 = *run.nStep;
@@ -93,7 +97,10 @@ int batch_queue(LoneRun& run, int m, LoneBatch* b) {
     if (rc == 0 && H && history_batch_queue(c, n, slot, dt0, *H->tHist, H->dtHist)) rc = RGPU_EHIP;
     if (rc == 0) rc = (step_pre(c, n) || step_core(c, n, 0.0, 0.0) || step_post_a(c, n, 0.0, 0.0) || step_post_b(c, n)) ? RGPU_EHIP : 0;
     if (rc == 0 && !c->rec.slots((n + 1) % 2)) rc = RGPU_EHIP;   // (cannot happen: same configuration, same kernels)
-    if (rc == 0 && M && M->due(n + 1) && monitor_batch_queue(c, (n + 1) & 1, slot)) rc = RGPU_EHIP;
+    if (rc == 0 && M && M->due(n + 1)) {
+      if (monitor_batch_queue(c, M->planes, (n + 1) & 1, b->samples)) rc = RGPU_EHIP;
+      else ++b->samples;
+    }
     if (rc) { c->clk_n = slot; break; }   // the record of the step that failed to queue is not read back
   }
   if (rc) { b->failed = true; b->launch_err = c->err + " " + rg_last_error_string(); }
@@ -109,20 +116,23 @@ int batch_harvest(LoneRun& run, const LoneBatch& b) {
   const MonRun* M = run.mon;
   const int queued = b.queued, n0 = *run.nStep;
   // the logs travel with the clock records: queued behind them here, complete after the one synchronisation of rgpu_clock_close.  A
-  // history record behind the last head queued, a monitor slot no sample was queued for or whose step did not run: copied unwritten, not read
+  // history record behind the last head queued, a monitor slot whose step did not run: copied unwritten, not read
   const bool log_ok = !H || queued == 0 || c->hist.download((size_t)queued, c->stream) == 0;
-  const bool mon_ok = !M || queued == 0 || c->mon.download((size_t)queued * RGPU_MON_NQ, c->stream) == 0;
+  const bool mon_ok = !M || b.samples == 0 || monitor_batch_log(c, M->planes).download((size_t)b.samples * M->width, c->stream) == 0;
   const double t_open = *run.t;
   int ran = 0, stop = 0;
   if (const int rc = rgpu_clock_close(c, n0, &ran, run.t, run.dt, run.dt_log ? run.dt_log + run.done : 0, &stop)) return rc;
   *run.nStep += ran;
   run.done += ran;
   if (M && ran > 0) {   // the host knows the step numbers; that step n0 + r ran is what the records said
-    if (!mon_ok) { c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps_monitored: read-back of the log"); }
+    if (!mon_ok) { c->rec.forget(); return fail(c, RGPU_EHIP, std::string(M->who) + ": read-back of the log"); }
+    const double* log = monitor_batch_log(c, M->planes).h;
     double ta = t_open;
-    for (int r = 0; r < ran; ++r) {
+    for (int r = 0, k = 0; r < ran; ++r) {
       ta += c->clk.h[r].dt;   // (*t as rgpu_clock_close accumulated it)
-      if (M->due(n0 + r + 1)) M->put(n0 + r + 1, ta, c->mon.h + (size_t)r * RGPU_MON_NQ);
+      if (!M->due(n0 + r + 1)) continue;
+      std::memcpy(M->slot(), log + (size_t)k++ * M->width, M->width * sizeof(double));   // the k-th sample queued: the qualifying steps in order
+      M->put(n0 + r + 1, ta);
     }
   }
   if (H && ran > 0) {   // a step that ran had its head queued in front of it: records [0, ran) are written
@@ -149,7 +159,7 @@ int run_steps_impl(LoneRun& run) {
   struct Current { rgpu_ctx* c; const int* n; ~Current() { c->cur = *n & 1; } } current = {c, run.nStep};   // however the loop is left: U[*nStep % 2] is the state
   (void)current;
   while (run.done < run.nsteps && *run.t < run.tEnd && !run.why) {
-    if (!clock_ready(c, *run.nStep % 2) || (run.hist && !run.hist->batch) || (run.mon && !monitor_scratch_fits(c))) {
+    if (!clock_ready(c, *run.nStep % 2) || (run.hist && !run.hist->batch) || (run.mon && !monitor_sample_fits(c, run.mon->planes))) {
       if (const int rc = literal_turn(run)) return rc;
       continue;
     }
@@ -202,7 +212,25 @@ int rgpu_run_steps_monitored(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, d
   if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, "run_steps_monitored: single-domain contexts only (a slab holds a part of the box)");
   if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_monitored: nsteps is negative");
   if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_monitored: every must be at least 1");
-  const MonRun M = {every, mon_n, mon_step, mon_t, mon};
+  const MonRun M = {every, false, (size_t)RGPU_MON_NQ, mon_n, mon_step, mon_t, mon, "run_steps_monitored"};
+  LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
+  return run_steps_impl(run);
+}
+
+long rgpu_monitor_planes_batch_samples(rgpu_ctx* c) { return c ? c->monp_samples : 0; }
+
+int rgpu_run_steps_monitored_planes(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int every,
+                                    int* mon_n, int* mon_step, double* mon_t, double* mon) {
+  RG_CHECK_CTX(c);
+  if (!nStep || !t || !dt || !mon_n || !mon_step || !mon_t || !mon) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: null pointer");
+  *mon_n = 0;
+  if (!c->U[0]) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: context without state");
+  if (!c->g.three_d) return fail(c, RGPU_EUNSUPPORTED, "run_steps_monitored_planes: 3D contexts only (the rows are the interior planes of a volume)");
+  if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: single-domain contexts only (a slab holds a part of the box)");
+  if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: nsteps is negative");
+  if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: every must be at least 1");
+  if (!monitor_planes_scratch_fits(c)) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: no scratch for the partial sums");
+  const MonRun M = {every, true, monp_sample_doubles(c->g), mon_n, mon_step, mon_t, mon, "run_steps_monitored_planes"};
   LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
   return run_steps_impl(run);
 }

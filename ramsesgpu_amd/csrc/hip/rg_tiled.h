@@ -16,3 +16,6 @@
 #include "monitor3d.h"
 // the gfx950 kernels of a lone context's monitor exist (api/monitor.h: without this macro it runs the flat functors)
 #define RGPU_TILED_MONITOR3D 1
+#include "monitor_profile.h"
+// the gfx950 kernels of the plane monitor exist (api/monitor.h: without this macro it runs the flat functors)
+#define RGPU_TILED_MONITOR_PROFILE 1

@@ -3,9 +3,11 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <iterator>
+#include <limits>
 #include <cstdint>
 #include <cstdio>
 #include <fstream>
@@ -715,6 +717,10 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
   // significant digits (the doubles round-trip).  The quiet turns go through rgpu_run_steps_monitored (the samples taken on the device
   // inside the device-clock batches); with a history file as well the loop keeps its history handling, is cut at the sampling steps
   // and takes the rows by the direct calls -- the same doubles either way.  Not for z-slab runs (a slab holds a part of the box).
+  // With planes=yes as well (3D single-domain runs) <outputDir>/<outputPrefix>_monitor_planes.txt gets the sixteen doubles of every
+  // interior plane (rgpu_state_monitor_planes, "plane monitors") at the same steps, one line per plane; the samples then come from
+  // rgpu_run_steps_monitored_planes / rgpu_state_monitor_planes, and the rows of the monitor file are folded from the plane rows on
+  // the host, ascending in k, by the identity of include/rgpu.h: the bytes a run without planes=yes writes.
   const bool monitorEnabled = cfg_.get_bool("monitor", "enabled", false);
   const int mon_every = monitorEnabled ? (int)cfg_.get_integer("monitor", "every", 10) : 0;
   if (monitorEnabled && mon_every < 1) throw std::runtime_error("[monitor] every must be at least 1");
@@ -734,7 +740,43 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
       f << "\n";
     }
   };
+  const bool planesWanted = monitorEnabled && cfg_.get_bool("monitor", "planes", false);
+  bool noted_planes = false;
+  if (planesWanted && monitor_on && p_.nz_global == 1) note_once(&noted_planes, "2D run: the plane monitor file is not written");
+  const bool planes_on = planesWanted && monitor_on && p_.nz_global != 1;
+  const std::string planes_path = planes_on ? rs_.outputDir + "/" + rs_.outputPrefix + "_monitor_planes.txt" : std::string();
+  const size_t planes_nz = (size_t)p_.nz;
+  // n samples of planes_nz rows each: the lines of the planes file, and the monitor rows they fold to
+  const auto planes_rows = [&](int n, const int* step, const double* t, const double* v) {
+    std::ofstream f(planes_path.c_str(), std::ios::app);
+    if (!f) throw std::runtime_error("cannot write " + planes_path);
+    std::vector<double> folded((size_t)n * RGPU_MON_NQ);
+    char num[40];
+    for (int k = 0; k < n; ++k) {
+      double* a = &folded[(size_t)k * RGPU_MON_NQ];
+      for (int q = 0; q < RGPU_MON_NQ; ++q) a[q] = (q == 7 || q == 8) ? std::numeric_limits<double>::infinity() : 0.0;
+      for (size_t kk = 0; kk < planes_nz; ++kk) {
+        const double* row = v + ((size_t)k * planes_nz + kk) * RGPU_MONP_NQ;
+        f << step[k];
+        std::snprintf(num, sizeof(num), " %.17g", t[k]);
+        f << num << " " << kk;
+        for (int q = 0; q < RGPU_MONP_NQ; ++q) { std::snprintf(num, sizeof(num), " %.17g", row[q]); f << num; }
+        f << "\n";
+        for (int q = 0; q < 7; ++q) a[q] = a[q] + row[q];
+        a[7] = std::fmin(a[7], row[7]); a[8] = std::fmin(a[8], row[8]); a[9] = std::fmax(a[9], row[9]);
+      }
+    }
+    f.close();
+    monitor_rows(n, step, t, folded.data());
+  };
+  std::vector<double> planes_v;
   const auto monitor_direct = [&](int n) {   // the row of the current state U[n % 2]
+    if (planes_on) {
+      planes_v.resize(std::max(planes_v.size(), planes_nz * RGPU_MONP_NQ));
+      check(rgpu_state_monitor_planes(ctx_, n % 2, planes_v.data()), "state_monitor_planes");
+      planes_rows(1, &n, &totalTime_, planes_v.data());
+      return;
+    }
     double v[RGPU_MON_NQ];
     check(p_.nz_global != 1 ? rgpu_state_monitor3d(ctx_, n % 2, v) : rgpu_state_monitor(ctx_, n % 2, v), "state_monitor");
     monitor_rows(1, &n, &totalTime_, v);
@@ -743,6 +785,11 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     std::ofstream f(mon_path.c_str(), std::ios::trunc);
     if (!f) throw std::runtime_error("cannot write " + mon_path);
     f << "# nStep totalTime " RGPU_MON_NAMES "\n";
+  }
+  if (planes_on && !(totalTime_ > 0)) {
+    std::ofstream f(planes_path.c_str(), std::ios::trunc);
+    if (!f) throw std::runtime_error("cannot write " + planes_path);
+    f << "# nStep totalTime k " RGPU_MONP_NAMES "\n";
   }
   std::vector<int> mon_step;
   std::vector<double> mon_t, mon_v;
@@ -779,7 +826,15 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     const bool monitor_batched = monitor_on && !historyEnabled && quiet > 1;
     if (monitor_on && !monitor_batched && mon_every - nStep % mon_every < quiet) quiet = mon_every - nStep % mon_every;   // the direct call follows
     const int nStep_before = nStep;
-    if (monitor_batched) {
+    if (monitor_batched && planes_on) {
+      int mn = 0;
+      const size_t cap = (size_t)(quiet / mon_every + 1);
+      if (mon_step.size() < cap) { mon_step.resize(cap); mon_t.resize(cap); }
+      if (planes_v.size() < cap * planes_nz * RGPU_MONP_NQ) planes_v.resize(cap * planes_nz * RGPU_MONP_NQ);
+      const int rc = rgpu_run_steps_monitored_planes(ctx_, quiet, rs_.tEnd, &nStep, &totalTime_, &dt, 0, mon_every, &mn, mon_step.data(), mon_t.data(), planes_v.data());
+      planes_rows(mn, mon_step.data(), mon_t.data(), planes_v.data());
+      if (rc < 0) check(rc, "run_steps_monitored_planes");
+    } else if (monitor_batched) {
       int mn = 0;
       const size_t cap = (size_t)(quiet / mon_every + 1);
       if (mon_step.size() < cap) { mon_step.resize(cap); mon_t.resize(cap); mon_v.resize(cap * RGPU_MON_NQ); }

@@ -17,7 +17,7 @@ from ._capi import RgpuParams
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # the series out of run_steps_monitored (of a Solver, of one member of an Ensemble): step numbers [n], times [n], values [n, 10]
-# (columns _capi.MON_NAMES)
+# (columns _capi.MON_NAMES); out of run_steps_monitored_planes: values [n, nz, 16] (columns _capi.MONP_NAMES)
 MonitorSeries = collections.namedtuple("MonitorSeries", "step t values")
 
 
@@ -282,6 +282,34 @@ class Solver:
             self._chk(done, "run_steps_monitored")
         self.dt_log = [log[i] for i in range(done)]
         return done, self.monitor_series
+
+    def state_monitor_planes(self, parity=None):
+        """the plane monitor of U[parity] (default: nStep % 2) of a 3D state: ndarray [nz, 16], one row per interior plane, columns
+        _capi.MONP_NAMES -- the ten monitor quantities of the plane, then the sums of the cell-centred field, bx by, rho vx vy and
+        rho^2 (rgpu_state_monitor_planes; include/rgpu.h)"""
+        out = np.zeros((self.p.nz, _capi.MONP_NQ))
+        par = self.nStep % 2 if parity is None else int(parity)
+        self._chk(self.lib.rgpu_state_monitor_planes(self.ctx, par, out.ctypes.data_as(_capi.c_double_p)), "state_monitor_planes")
+        return out
+
+    def run_steps_monitored_planes(self, nsteps, every, tEnd=float("inf")):
+        """run_steps with a plane-monitor sample after every step that brings nStep to a multiple of `every`
+        (rgpu_run_steps_monitored_planes: inside the device-clock batches the samples are taken on the device, one read-back per
+        batch).  Returns (done, MonitorSeries): the steps done and the samples of this call -- .step [n], .t [n] (the time after that
+        step), .values [n, nz, 16] (_capi.MONP_NAMES)"""
+        cap = max(int(nsteps), 0) // max(int(every), 1) + 1
+        n, t, d, mn = C.c_int(self.nStep), C.c_double(self.totalTime), C.c_double(self.dt), C.c_int(0)
+        log = (C.c_double * max(int(nsteps), 1))()
+        mstep, mt, mv = np.zeros(cap, dtype=np.intc), np.zeros(cap), np.zeros((cap, self.p.nz, _capi.MONP_NQ))
+        done = self.lib.rgpu_run_steps_monitored_planes(self.ctx, int(nsteps), float(tEnd), C.byref(n), C.byref(t), C.byref(d), log, int(every), C.byref(mn),
+                                                        mstep.ctypes.data_as(C.POINTER(C.c_int)), mt.ctypes.data_as(_capi.c_double_p), mv.ctypes.data_as(_capi.c_double_p))
+        k = mn.value
+        self.nStep, self.totalTime, self.dt = n.value, t.value, d.value   # (they describe the steps that ran, also when the call failed)
+        self.monitor_planes_series = MonitorSeries(mstep[:k].astype(int), mt[:k].copy(), mv[:k].copy())
+        if done < 0:
+            self._chk(done, "run_steps_monitored_planes")
+        self.dt_log = [log[i] for i in range(done)]
+        return done, self.monitor_planes_series
 
     def history_turbulence(self, nStep=None):
         """history_turbulence (MHDRunBase.cpp:3626-3810) reduced on the device: the 18 columns after totalTime and dt"""
