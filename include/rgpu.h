@@ -659,6 +659,74 @@ int rgpu_run_steps_monitored_planes(rgpu_ctx* c, int nsteps, double tEnd, int* n
                                     double* mon /* [cap][nz][RGPU_MONP_NQ] */);
 long rgpu_monitor_planes_batch_samples(rgpu_ctx* c);
 
+/* ---- map monitors: slices and projections of a 3D state, taken on the device ---------------------------------------------------------
+ * What one looks at first in a 3D run is a picture: the mid-plane density of an implosion or a jet, an x-z cut of By in an MRI box,
+ * the column density of a turbulent box along each axis.  A map is a 2D array of RGPU_MAP_NQ = 12 channels taken from U[parity] of a
+ * single-domain 3D context as the array stands, hydro or MHD, shearing box included.  No ghost fill is done; the high faces of the last
+ * interior row, column and plane come from the first ghost layer, as for the monitors.  A map is given by a spec:
+ *     axis   0 = x, 1 = y, 2 = z: the direction summed over (w)
+ *     lo, hi the range [lo, hi) of interior indices along it, 0 <= lo < hi <= n_axis
+ * Channels, in the order of RGPU_MAP_NAMES: channel q of a cell is column {0, 1, 2, 3, 4, 5, 6, 8, 10, 11, 12, 15}[q] of the plane
+ * monitor's per-cell terms above (rho = its "mass" term, eint = its "min_eint" term (E - ekin) - emag, rho2 = rho * rho): the same
+ * operations in the same order, no FMA contraction in either library (csrc/kernels_monitor_maps.h picks them, it restates nothing).
+ * For a hydro state the channels emag, bx, by, bz are exactly +0.0.
+ * Pixel: out[q][v][u] = the sum over w = lo .. hi - 1 of channel q of the cell, ascending in w, from +0.0, "a = a + x" at every step;
+ * no floating-point atomics, no segments, no butterfly.  The remaining axes (u, v), u varying fastest in memory:
+ *     axis z: u = i, v = j, [12][ny][nx]      axis y: u = i, v = k, [12][nz][nx]      axis x: u = j, v = k, [12][nz][ny]
+ * A slice is the map whose range holds one cell, hi == lo + 1: +0.0 + term, the term itself (a term of -0.0 becomes +0.0).  One
+ * definition and one code path for slices and projections.  A value depends on the state and the spec only -- not on the library, on
+ * whether the sample is taken inside a batch, on which kernel ran, or on how the kernels cut the grid.
+ * NaN: IEEE addition.  A NaN term makes the one pixel whose column holds it NaN in the channels that contain it and changes nothing
+ * else: a NaN density gives NaN in rho, ekin, eint and rho2 of that pixel; mx, my, mz, E, emag, bx, by, bz keep their numbers.
+ * Against the monitor: the sum over the pixels of each of channels 0 - 6 of the full z map lies within N 2^-53 sum|terms| (N = nx ny
+ * nz), the bound of any summation order stated for the monitors above, of the same column of rgpu_state_monitor3d.
+ * (tests/monitor_maps_checks.py is this definition in numpy.)
+ *
+ *   rgpu_map_doubles       the doubles of the map of *spec on this context, RGPU_MAP_NQ x nv x nu; 0 for a spec (or a context) that
+ *                          rgpu_state_maps would refuse.
+ *   rgpu_state_maps        nmaps maps of U[parity], one after another in `out` (map m at the sum of rgpu_map_doubles of the specs
+ *                          before it).  Reads the state only: ghost cells, CFL slots and what the context knows about them stay as
+ *                          they are.  One launch per map, each writing straight to its place in a device buffer (the head of the map
+ *                          log below, grown to one sample where it is smaller, whatever the budget); one read-back for all maps.
+ *                          Synchronises.
+ *   rgpu_run_steps_mapped  rgpu_run_steps_log (same states, same dt sequence, same return value) plus sampling, with the semantics of
+ *                          rgpu_run_steps_monitored_planes word for word: a sample (all nmaps maps) after each step that brings
+ *                          *nStep to a multiple of `every`; *mon_n = the samples of this call (<= cap = nsteps / every + 1); sample
+ *                          k: mon_step[k], mon_t[k] the host-accumulated *t after that step, maps + k * W (W = the sum of
+ *                          rgpu_map_doubles over the specs) what rgpu_state_maps gives on that state, bit for bit.  A step that
+ *                          reaches tEnd is sampled if it qualifies, nothing is sampled after a stop; *mon_n counts only samples whose
+ *                          values were written.  A run cut into calls gives the series of one call.  dt_log may be NULL.
+ *                          Where the context takes its time step from the device (rgpu_device_time_step_ready) the kernels of a
+ *                          sample (csrc/hip/monitor_maps.h) are queued behind the last kernel of each qualifying step, return in
+ *                          their first instructions when the step's clock record says stop, and write to a device log that is copied
+ *                          back once per batch with the clock records: no synchronisation inside a batch.  Everywhere else (first
+ *                          steps, gravity, the dissipative stage, forcing, phase timers, option "step_clock" = 0) the call is the
+ *                          literal loop: rgpu_one_step_integration, then rgpu_state_maps.
+ *                          Memory: maps need no scratch, the flux array is not used.  The log of a batch has a byte budget, option
+ *                          "map_log_kib" (default 262144: 256 MiB on the device and as much pinned): slots = min(RGPU_CLOCK_BATCH /
+ *                          every + 1, budget / bytes of a sample), and a batch is cut so that it holds no more samples than slots.
+ *                          A sample larger than the budget: the literal loop.  The log and its pinned mirror are allocated by the
+ *                          first call that needs them, grown between batches if a later call needs more, freed with the context,
+ *                          and are not part of rgpu_device_bytes.
+ *   rgpu_map_batch_samples how many samples (of nmaps maps each) this context has queued on the device inside its batches so far (0
+ *                          where every call took the literal loop), as rgpu_monitor_planes_batch_samples.  These calls leave
+ *                          rgpu_monitor_batch_samples and rgpu_monitor_planes_batch_samples alone.
+ *   Errors (nothing has run, *mon_n == 0): RGPU_EUNSUPPORTED for a 2D context ("3D" in the message: a download is its map);
+ *                          RGPU_EINVAL for a slab context (slab_count > 1), a NULL pointer among nStep, t, dt, specs, mon_n,
+ *                          mon_step, mon_t, maps / out, nsteps < 0, every < 1 ("every" in the message), nmaps outside 1 ..
+ *                          RGPU_MAP_MAX, an axis outside 0 .. 2 or a range that is not 0 <= lo < hi <= n_axis (the message names
+ *                          the index of the offending map, "map 2: ..."). */
+#define RGPU_MAP_NQ 12
+#define RGPU_MAP_NAMES "rho mx my mz E ekin emag eint bx by bz rho2"   /* the RGPU_MAP_NQ channels, in order */
+#define RGPU_MAP_MAX 8                                                /* specs per call */
+typedef struct { int axis; int lo; int hi; } rgpu_map_spec;   /* axis 0 = x, 1 = y, 2 = z: the direction summed over; [lo, hi) in interior indices along it */
+size_t rgpu_map_doubles(rgpu_ctx* c, const rgpu_map_spec* spec);
+int rgpu_state_maps(rgpu_ctx* c, int parity, int nmaps, const rgpu_map_spec* specs, double* out);
+int rgpu_run_steps_mapped(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log,
+                          int every, int nmaps, const rgpu_map_spec* specs, int* mon_n, int* mon_step /* [cap] */, double* mon_t /* [cap] */,
+                          double* maps /* [cap][sum of rgpu_map_doubles] */);
+long rgpu_map_batch_samples(rgpu_ctx* c);
+
 /* Self-test of the device arithmetic the parity contract rests on: for n operand pairs computes on the device
  *   quot[i]  = rg_div(num[i], rg_recip(den[i]))   the shared-reciprocal division of csrc/hip/rg_backend.h
  *   quot2[i] = num[i] / den[i]                    the compiler's IEEE division
@@ -701,7 +769,10 @@ int rgpu_selftest_alfven(const rgpu_params* p, int n, const double* states36, do
  *   "history_batch" (1) rgpu_run_steps_history samples on the device inside the device-clock batches; 0: its literal loop everywhere
  *   "member_params" (0) 1: the fused rounds of EVERY ensemble read their constants from the per-member table (the path of a
  *                       parameter scan), even when all sets are equal: the table path and the by-value path on one workload
- * rgpu_set_option returns the previous value (-1: unknown name; the options above are never negative except "as created"). */
+ *   "map_log_kib" (262144) byte budget, in KiB, of the device log of the maps a batch of rgpu_run_steps_mapped samples ("map monitors")
+ *   "map_x_tiled" (-1)  which kernel sums a map along x: -1 by the thickness of the range, 0 the direct one, 1 the tiled one (the same bits)
+ * rgpu_set_option returns the previous value (-1: unknown name; the options above are never negative except "as created" and the
+ * default of "map_x_tiled"). */
 int rgpu_set_option(const char* name, int value);
 int rgpu_get_option(const char* name);
 

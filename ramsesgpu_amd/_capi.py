@@ -13,6 +13,10 @@ MON_NQ = len(MON_NAMES)
 # the columns of a row of the plane monitor (rgpu_state_monitor_planes, rgpu_run_steps_monitored_planes): RGPU_MONP_NQ = 16
 MONP_NAMES = MON_NAMES + ("bx", "by", "bz", "bxby", "rvxvy", "rho2")
 MONP_NQ = len(MONP_NAMES)
+# the channels of a map (rgpu_state_maps, rgpu_run_steps_mapped): RGPU_MAP_NQ = 12, columns 0 1 2 3 4 5 6 8 10 11 12 15 of the plane monitor's terms
+MAP_NAMES = ("rho", "mx", "my", "mz", "E", "ekin", "emag", "eint", "bx", "by", "bz", "rho2")
+MAP_NQ = len(MAP_NAMES)
+MAP_MAX = 8
 T_NAMES = ["boundaries", "prim", "elec", "trace", "flux", "emf", "update", "shear", "dt", "dissipative", "sweep"]
 
 
@@ -69,6 +73,11 @@ class RgpuParams(C.Structure):
 
 
 c_double_p = C.POINTER(C.c_double)
+
+
+class RgpuMapSpec(C.Structure):
+    """rgpu_map_spec: axis 0 = x, 1 = y, 2 = z, the direction summed over; [lo, hi) in interior indices along it"""
+    _fields_ = [("axis", C.c_int), ("lo", C.c_int), ("hi", C.c_int)]
 
 
 def declare_host_api(lib):
@@ -230,6 +239,16 @@ def declare_device_api(lib):
                                                         C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]
         lib.rgpu_monitor_planes_batch_samples.restype = C.c_long
         lib.rgpu_monitor_planes_batch_samples.argtypes = [ctx]
+    if hasattr(lib, "rgpu_state_maps"):   # (absent from an older build of the library: scripts/monitor_maps_bench.py --baseline-lib)
+        lib.rgpu_map_doubles.restype = C.c_size_t
+        lib.rgpu_map_doubles.argtypes = [ctx, C.POINTER(RgpuMapSpec)]
+        lib.rgpu_state_maps.restype = C.c_int
+        lib.rgpu_state_maps.argtypes = [ctx, C.c_int, C.c_int, C.POINTER(RgpuMapSpec), c_double_p]
+        lib.rgpu_run_steps_mapped.restype = C.c_int
+        lib.rgpu_run_steps_mapped.argtypes = [ctx, C.c_int, C.c_double, C.POINTER(C.c_int), c_double_p, c_double_p, c_double_p, C.c_int,
+                                              C.c_int, C.POINTER(RgpuMapSpec), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]
+        lib.rgpu_map_batch_samples.restype = C.c_long
+        lib.rgpu_map_batch_samples.argtypes = [ctx]
     return lib
 
 
@@ -281,4 +300,5 @@ DECLARED_SYMBOLS = [
     "rgpu_state_monitor", "rgpu_ensemble_monitor", "rgpu_ensemble_run_steps_monitored", "rgpu_ensemble_monitor_device_bytes",
     "rgpu_state_monitor3d", "rgpu_run_steps_monitored", "rgpu_monitor_batch_samples",
     "rgpu_state_monitor_planes", "rgpu_run_steps_monitored_planes", "rgpu_monitor_planes_batch_samples",
+    "rgpu_map_doubles", "rgpu_state_maps", "rgpu_run_steps_mapped", "rgpu_map_batch_samples",
 ]

@@ -103,6 +103,12 @@ struct rgpu_ctx {
   DeviceMirror<double> monp;
   size_t monp_slots = 0;
   long monp_samples = 0;        // plane-monitor samples queued on the device so far (rgpu_monitor_planes_batch_samples)
+  // the maps (kernels_monitor_maps.h; rgpu_state_maps, rgpu_run_steps_mapped): the device buffer the kernels of a sample write to --
+  // one sample taken outside a batch at its head, or the samples of a batch, as many as the budget (option "map_log_kib") and the
+  // cadence allow; monm_doubles doubles, allocated by the first call that needs them, grown by a later one that needs more
+  DeviceMirror<double> monm;
+  size_t monm_doubles = 0;
+  long monm_samples = 0;        // map samples queued on the device inside batches so far (rgpu_map_batch_samples)
   // fused 2D steps: the clock is folded into the step kernel itself (step_clock_rec.h: ClockFold) over three rotating slot arrays;
   // d_red always points at the array that holds the maxima of the current state
   unsigned long long* d_red_base = 0;   // 3 x RG_DT_SLOTS

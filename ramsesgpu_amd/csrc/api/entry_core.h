@@ -309,6 +309,11 @@ int rgpu_state_checksum(rgpu_ctx* c, int parity, unsigned long long* out) {
 int rgpu_state_monitor(rgpu_ctx* c, int parity, double* out) { return state_monitor(c, false, parity, out); }
 int rgpu_state_monitor3d(rgpu_ctx* c, int parity, double* out) { return state_monitor(c, true, parity, out); }
 int rgpu_state_monitor_planes(rgpu_ctx* c, int parity, double* out) { return state_monitor_planes(c, parity, out); }
+int rgpu_state_maps(rgpu_ctx* c, int parity, int nmaps, const rgpu_map_spec* specs, double* out) { return state_maps(c, parity, nmaps, specs, out); }
+size_t rgpu_map_doubles(rgpu_ctx* c, const rgpu_map_spec* spec) {
+  if (!c || !spec || !c->U[0] || !c->g.three_d || c->p.slab_count > 1 || !map_spec_error(c, *spec).empty()) return 0;
+  return map_doubles(c, *spec);
+}
 
 double rgpu_compute_dt(rgpu_ctx* c, int useU) {
   double v = 0;

@@ -1,6 +1,7 @@
 // api/monitor.h -- the monitor of a lone context on the host side (kernels_monitor.h): scratch extent and launches of one sample, for
 // rgpu_state_monitor (2D), rgpu_state_monitor3d and a sample queued inside a device-clock batch (rgpu_run_steps_monitored); the same for
-// the plane monitor (kernels_monitor_planes.h: rgpu_state_monitor_planes, rgpu_run_steps_monitored_planes).  See api/ctx.h.
+// the plane monitor (kernels_monitor_planes.h: rgpu_state_monitor_planes, rgpu_run_steps_monitored_planes) and for the map monitor
+// (kernels_monitor_maps.h: rgpu_state_maps, rgpu_run_steps_mapped).  See api/ctx.h.
 #pragma once
 namespace {
 // One route for either dimension, a 2D state being a volume of one plane.  Everything on the device, the sum over the planes included,
@@ -75,20 +76,118 @@ int state_monitor_planes(rgpu_ctx* c, int parity, double* out) {
   return RGPU_OK;
 }
 
-// ---- the samples of a batch: of the monitor, or (planes) of the plane monitor ------------------------------------------------------
-size_t monitor_sample_doubles(const rgpu_ctx* c, bool planes) { return planes ? monp_sample_doubles(c->g) : (size_t)MON_NQ; }
-bool monitor_sample_fits(rgpu_ctx* c, bool planes) { return planes ? monitor_planes_scratch_fits(c) : monitor_scratch_fits(c); }
-DeviceMirror<double>& monitor_batch_log(rgpu_ctx* c, bool planes) { return planes ? c->monp : c->mon; }
-// The log of a call that samples every `every` steps.  The monitor's: a slot per step of a batch.  The plane monitor's: a slot per
-// sample that can fall into one batch, grown (between two batches: nothing is in flight) if this call needs more than the last did
-int monitor_batch_alloc(rgpu_ctx* c, bool planes, int every) {
-  DeviceMirror<double>& log = monitor_batch_log(c, planes);
-  const size_t slots = planes ? (size_t)rgpu_ctx::kClockBatch / (size_t)every + 1 : (size_t)rgpu_ctx::kClockBatch;
-  if (planes && log.allocated() && c->monp_slots < slots) log.release();
+// ---- the map monitor (kernels_monitor_maps.h): the same consumer with a third sample, nmaps pictures of MAP_NQ channels ------------
+static_assert(MAP_NQ == RGPU_MAP_NQ, "include/rgpu.h states the channels of a map");
+// "" for a spec this context can take, else what is wrong with it
+std::string map_spec_error(const rgpu_ctx* c, const rgpu_map_spec& s) {
+  if (s.axis < 0 || s.axis > 2) return "axis must be 0 (x), 1 (y) or 2 (z)";
+  const int n = s.axis == 0 ? c->g.nx : s.axis == 1 ? c->g.ny : c->g.nz;
+  if (!(0 <= s.lo && s.lo < s.hi && s.hi <= n)) return "the range must satisfy 0 <= lo < hi <= " + std::to_string(n);
+  return "";
+}
+size_t map_doubles(const rgpu_ctx* c, const rgpu_map_spec& s) { return (size_t)MAP_NQ * map_pixels(map_geom(c->g, s.axis, s.lo, s.hi)); }
+size_t maps_sample_doubles(const rgpu_ctx* c, int nmaps, const rgpu_map_spec* specs) {
+  size_t n = 0;
+  for (int m = 0; m < nmaps; ++m) n += map_doubles(c, specs[m]);
+  return n;
+}
+// what rgpu_state_maps and rgpu_run_steps_mapped refuse alike, in this order; 0: the maps can be taken
+int maps_refusal(rgpu_ctx* c, const std::string& who, int nmaps, const rgpu_map_spec* specs) {
+  if (!c->U[0]) return fail(c, RGPU_EINVAL, who + ": context without state");
+  if (!c->g.three_d) return fail(c, RGPU_EUNSUPPORTED, who + ": 3D contexts only (the download of a 2D state is its map)");
+  if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, who + ": single-domain contexts only (a slab holds a part of the box)");
+  if (nmaps < 1 || nmaps > RGPU_MAP_MAX) return fail(c, RGPU_EINVAL, who + ": nmaps must be 1 .. " + std::to_string(RGPU_MAP_MAX));
+  for (int m = 0; m < nmaps; ++m) {
+    const std::string why = map_spec_error(c, specs[m]);
+    if (!why.empty()) return fail(c, RGPU_EINVAL, who + ": map " + std::to_string(m) + ": " + why);
+  }
+  return RGPU_OK;
+}
+// the device buffer the kernels of the maps write to, at least `doubles` long: grown between two batches or two calls, when nothing
+// is in flight.  != 0: it is not there
+int map_log_reserve(rgpu_ctx* c, size_t doubles) {
+  if (c->monm.allocated() && c->monm_doubles >= doubles) return 0;
+  c->monm.release();
+  c->monm_doubles = 0;
+  if (c->monm.alloc(doubles) == 0 && rg_memset_async(c->monm.d, 0, doubles * sizeof(double), c->stream) == 0) {
+    c->monm_doubles = doubles;
+    return 0;
+  }
+  c->monm.release();   // zeroed, or not there
+  return -1;
+}
+// the doubles the option "map_log_kib" gives the log of a batch
+size_t map_log_budget_doubles() {
+  const int kib = rgpu::options().map_log_kib;
+  return kib > 0 ? (size_t)kib * (1024 / sizeof(double)) : 0;
+}
+// queues the maps of U one after another into dst (device), one launch each; clk != 0: the record that decides, on the device,
+// whether they are taken.  The one place that knows whether the backend has kernels of its own
+int maps_queue(rgpu_ctx* c, const double* U, const StepClock* clk, int nmaps, const rgpu_map_spec* specs, double* dst) {
+  for (int m = 0; m < nmaps; ++m) {
+    const rgpu_map_spec& s = specs[m];
+#ifdef RGPU_TILED_MONITOR_MAPS
+    if (rgpu_tiled::launch_monitor_map(c->stream, c->g, s.axis, s.lo, s.hi, rgpu::options().map_x_tiled, U, clk, dst)) return -1;
+#else
+    const MapGeom g = map_geom(c->g, s.axis, s.lo, s.hi);
+    K_mon_map k = {c->g, g, U, dst, clk};
+    if (rg_launch<kBlock>(c->stream, (unsigned)map_pixels(g), k)) return -1;
+#endif
+    dst += map_doubles(c, s);
+  }
+  return 0;
+}
+int state_maps(rgpu_ctx* c, int parity, int nmaps, const rgpu_map_spec* specs, double* out) {
+  RG_CHECK_CTX(c);
+  const std::string who = "state_maps";
+  if (!out || !specs) return fail(c, RGPU_EINVAL, who + ": null pointer");
+  if (const int rc = maps_refusal(c, who, nmaps, specs)) return rc;
+  const size_t n = maps_sample_doubles(c, nmaps, specs);
+  if (map_log_reserve(c, n)) return RG_HIPFAIL(c, who + ": device buffer of the maps");
+  if (maps_queue(c, c->U[parity & 1], 0, nmaps, specs, c->monm.d) || rg_copy_d2h(out, c->monm.d, n * sizeof(double), c->stream) || rg_stream_sync(c->stream))
+    return RG_HIPFAIL(c, who);
+  return RGPU_OK;
+}
+
+// ---- the samples of a batch: of the monitor, of the plane monitor, or of the map monitor ------------------------------------------
+// which sample a call takes (and, for maps, of what)
+enum MonWhat { MON_MONITOR, MON_PLANES, MON_MAPS };
+struct MonSample { MonWhat what; int nmaps; const rgpu_map_spec* specs; };
+size_t monitor_sample_doubles(const rgpu_ctx* c, const MonSample& S) {
+  return S.what == MON_MAPS ? maps_sample_doubles(c, S.nmaps, S.specs) : S.what == MON_PLANES ? monp_sample_doubles(c->g) : (size_t)MON_NQ;
+}
+// whether the samples of this context can be taken inside its device-clock batches.  Maps need no scratch: one sample within the budget
+bool monitor_sample_fits(rgpu_ctx* c, const MonSample& S) {
+  if (S.what == MON_MAPS) return c->g.three_d && monitor_sample_doubles(c, S) <= map_log_budget_doubles();
+  return S.what == MON_PLANES ? monitor_planes_scratch_fits(c) : monitor_scratch_fits(c);
+}
+DeviceMirror<double>& monitor_batch_log(rgpu_ctx* c, const MonSample& S) { return S.what == MON_MAPS ? c->monm : S.what == MON_PLANES ? c->monp : c->mon; }
+// The slots of the log of a call that samples every `every` steps.  The monitor's: a slot per step of a batch.  The plane monitor's:
+// a slot per sample that can fall into one batch.  The maps': as many, or as the budget holds if that is fewer (at least one:
+// monitor_sample_fits)
+size_t monitor_batch_slots(const rgpu_ctx* c, const MonSample& S, int every) {
+  if (S.what == MON_MONITOR) return (size_t)rgpu_ctx::kClockBatch;
+  const size_t slots = (size_t)rgpu_ctx::kClockBatch / (size_t)every + 1;
+  if (S.what == MON_PLANES) return slots;
+  const size_t held = map_log_budget_doubles() / monitor_sample_doubles(c, S);
+  return held < slots ? held : slots;
+}
+// How many of the m steps behind step n0 a batch takes: it ends at the last step before the (slots + 1)-th step that is due, so that
+// it holds no more samples than its log has slots (all m where the log has a slot for every sample of a full batch)
+int monitor_batch_steps(const rgpu_ctx* c, const MonSample& S, int every, int n0, int m) {
+  const long long over = ((long long)(n0 / every) + 1 + (long long)monitor_batch_slots(c, S, every)) * every;
+  return over - 1 - n0 < m ? (int)(over - 1 - n0) : m;
+}
+// The log: grown (between two batches: nothing is in flight) if this call needs more than the last did
+int monitor_batch_alloc(rgpu_ctx* c, const MonSample& S, int every) {
+  const size_t slots = monitor_batch_slots(c, S, every);
+  const size_t n = slots * monitor_sample_doubles(c, S);
+  if (S.what == MON_MAPS) return map_log_reserve(c, n);
+  DeviceMirror<double>& log = monitor_batch_log(c, S);
+  if (S.what == MON_PLANES && log.allocated() && c->monp_slots < slots) log.release();
   if (log.allocated()) return 0;
-  const size_t n = slots * monitor_sample_doubles(c, planes);
   if (log.alloc(n) == 0 && rg_memset_async(log.d, 0, n * sizeof(double), c->stream) == 0) {
-    if (planes) c->monp_slots = slots;
+    if (S.what == MON_PLANES) c->monp_slots = slots;
     return 0;
   }
   log.release();   // zeroed, or not there
@@ -96,10 +195,11 @@ int monitor_batch_alloc(rgpu_ctx* c, bool planes, int every) {
 }
 // Queues, behind the last kernel of the step whose record is c->clk_cur, the sample of U[parity], the state that step leaves: into
 // slot k of the log -- k samples were queued in the open batch before it -- if the record says that the step ran.
-int monitor_batch_queue(rgpu_ctx* c, bool planes, int parity, int k) {
-  double* dst = monitor_batch_log(c, planes).d + (size_t)k * monitor_sample_doubles(c, planes);
-  const int rc = planes ? monitor_planes_queue(c, c->U[parity & 1], c->clk_cur, dst) : monitor_queue(c, c->U[parity & 1], c->clk_cur, dst);
-  if (rc == 0) ++(planes ? c->monp_samples : c->mon_samples);
+int monitor_batch_queue(rgpu_ctx* c, const MonSample& S, int parity, int k) {
+  double* dst = monitor_batch_log(c, S).d + (size_t)k * monitor_sample_doubles(c, S);
+  const double* U = c->U[parity & 1];
+  const int rc = S.what == MON_MAPS ? maps_queue(c, U, c->clk_cur, S.nmaps, S.specs, dst) : S.what == MON_PLANES ? monitor_planes_queue(c, U, c->clk_cur, dst) : monitor_queue(c, U, c->clk_cur, dst);
+  if (rc == 0) ++(S.what == MON_MAPS ? c->monm_samples : S.what == MON_PLANES ? c->monp_samples : c->mon_samples);
   return rc;
 }
 

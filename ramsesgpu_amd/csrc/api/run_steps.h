@@ -1,4 +1,4 @@
-// api/run_steps.h -- entry points: the time loop of a lone context (rgpu_run_steps, _log, _history, _monitored, _monitored_planes; every member-alone round
+// api/run_steps.h -- entry points: the time loop of a lone context (rgpu_run_steps, _log, _history, _monitored, _monitored_planes, _mapped; every member-alone round
 // of an ensemble comes through here too).  One LoneRun per call; per turn either the reference's loop body (literal_turn) or a batch
 // of device-clock steps (api/entry_clock.h), queued by batch_queue and read back once by batch_harvest.  The two optional consumers
 // of a step -- the history row in front of it, the monitor sample behind it -- each write the caller's arrays in one place, put().
@@ -18,11 +18,12 @@ struct HistRun {
 };
 static_assert((int)HIST_BATCH_NQ == RGPU_HIST_NQ, "include/rgpu.h states the width of a history row");
 
-// what rgpu_run_steps_monitored and rgpu_run_steps_monitored_planes add to the loop: the cadence in steps, which of the two samples
-// is taken -- the monitor's RGPU_MON_NQ doubles, or (planes) the plane monitor's nz x RGPU_MONP_NQ -- and where the samples go (see
-// include/rgpu.h).  One consumer, two samples: api/monitor.h chooses the launches by `planes`
+// what rgpu_run_steps_monitored, rgpu_run_steps_monitored_planes and rgpu_run_steps_mapped add to the loop: the cadence in steps,
+// which of the three samples is taken -- the monitor's RGPU_MON_NQ doubles, the plane monitor's nz x RGPU_MONP_NQ, or the maps of
+// `what.specs` -- and where the samples go (see include/rgpu.h).  One consumer, three samples: api/monitor.h chooses the launches,
+// the log and its slots by `what`
 struct MonRun {
-  int every; bool planes; size_t width;      // width: the doubles of a sample
+  int every; MonSample what; size_t width;   // width: the doubles of a sample
   int* n; int* step; double* t; double* v;   // *n samples so far; step[k], t[k], v[k][width]
   const char* who;                           // the entry point, for messages
   bool due(int step_no) const { return step_no % every == 0; }   // the state step number step_no names is sampled
@@ -61,7 +62,9 @@ int literal_turn(LoneRun& run) {
   ++run.done;
   if (run.mon && run.mon->due(*run.nStep)) {
     const MonRun* M = run.mon;
-    if (const int rc = M->planes ? state_monitor_planes(c, *run.nStep & 1, M->slot()) : state_monitor(c, c->g.three_d != 0, *run.nStep & 1, M->slot())) return rc;
+    const int par = *run.nStep & 1;
+    if (const int rc = M->what.what == MON_MAPS ? state_maps(c, par, M->what.nmaps, M->what.specs, M->slot())
+                     : M->what.what == MON_PLANES ? state_monitor_planes(c, par, M->slot()) : state_monitor(c, c->g.three_d != 0, par, M->slot())) return rc;
     M->put(*run.nStep, *run.t);
   }
   return RGPU_OK;
@@ -83,7 +86,7 @@ int batch_queue(LoneRun& run, int m, LoneBatch* b) {
   const HistRun* H = run.hist;
   const MonRun* M = run.mon;
   // the logs of a batch: allocated by the first call that needs them
-  if (M && monitor_batch_alloc(c, M->planes, M->every)) return RG_HIPFAIL(c, std::string(M->who) + ": log of the batch");
+  if (M && monitor_batch_alloc(c, M->what, M->every)) return RG_HIPFAIL(c, std::string(M->who) + ": log of the batch");
   if (H && !c->hist.allocated() && c->hist.alloc(rgpu_ctx::kClockBatch)) return RG_HIPFAIL(c, "run_steps_history: log of the batch");
   if (const int rc = clock_open(c, *run.t, run.tEnd, true)) return rc;
   const int n0 = *run.nStep;
@@ -98,7 +101,7 @@ int batch_queue(LoneRun& run, int m, LoneBatch* b) {
     if (rc == 0) rc = (step_pre(c, n) || step_core(c, n, 0.0, 0.0) || step_post_a(c, n, 0.0, 0.0) || step_post_b(c, n)) ? RGPU_EHIP : 0;
     if (rc == 0 && !c->rec.slots((n + 1) % 2)) rc = RGPU_EHIP;   // (cannot happen: same configuration, same kernels)
     if (rc == 0 && M && M->due(n + 1)) {
-      if (monitor_batch_queue(c, M->planes, (n + 1) & 1, b->samples)) rc = RGPU_EHIP;
+      if (monitor_batch_queue(c, M->what, (n + 1) & 1, b->samples)) rc = RGPU_EHIP;
       else ++b->samples;
     }
     if (rc) { c->clk_n = slot; break; }   // the record of the step that failed to queue is not read back
@@ -118,7 +121,7 @@ int batch_harvest(LoneRun& run, const LoneBatch& b) {
   // the logs travel with the clock records: queued behind them here, complete after the one synchronisation of rgpu_clock_close.  A
   // history record behind the last head queued, a monitor slot whose step did not run: copied unwritten, not read
   const bool log_ok = !H || queued == 0 || c->hist.download((size_t)queued, c->stream) == 0;
-  const bool mon_ok = !M || b.samples == 0 || monitor_batch_log(c, M->planes).download((size_t)b.samples * M->width, c->stream) == 0;
+  const bool mon_ok = !M || b.samples == 0 || monitor_batch_log(c, M->what).download((size_t)b.samples * M->width, c->stream) == 0;
   const double t_open = *run.t;
   int ran = 0, stop = 0;
   if (const int rc = rgpu_clock_close(c, n0, &ran, run.t, run.dt, run.dt_log ? run.dt_log + run.done : 0, &stop)) return rc;
@@ -126,7 +129,7 @@ int batch_harvest(LoneRun& run, const LoneBatch& b) {
   run.done += ran;
   if (M && ran > 0) {   // the host knows the step numbers; that step n0 + r ran is what the records said
     if (!mon_ok) { c->rec.forget(); return fail(c, RGPU_EHIP, std::string(M->who) + ": read-back of the log"); }
-    const double* log = monitor_batch_log(c, M->planes).h;
+    const double* log = monitor_batch_log(c, M->what).h;
     double ta = t_open;
     for (int r = 0, k = 0; r < ran; ++r) {
       ta += c->clk.h[r].dt;   // (*t as rgpu_clock_close accumulated it)
@@ -159,13 +162,15 @@ int run_steps_impl(LoneRun& run) {
   struct Current { rgpu_ctx* c; const int* n; ~Current() { c->cur = *n & 1; } } current = {c, run.nStep};   // however the loop is left: U[*nStep % 2] is the state
   (void)current;
   while (run.done < run.nsteps && *run.t < run.tEnd && !run.why) {
-    if (!clock_ready(c, *run.nStep % 2) || (run.hist && !run.hist->batch) || (run.mon && !monitor_sample_fits(c, run.mon->planes))) {
+    if (!clock_ready(c, *run.nStep % 2) || (run.hist && !run.hist->batch) || (run.mon && !monitor_sample_fits(c, run.mon->what))) {
       if (const int rc = literal_turn(run)) return rc;
       continue;
     }
     const int left = run.nsteps - run.done;
+    int m = left < (int)rgpu_ctx::kClockBatch ? left : (int)rgpu_ctx::kClockBatch;
+    if (run.mon) m = monitor_batch_steps(c, run.mon->what, run.mon->every, *run.nStep, m);   // no more samples than the log has slots
     LoneBatch b;
-    if (const int rc = batch_queue(run, left < (int)rgpu_ctx::kClockBatch ? left : (int)rgpu_ctx::kClockBatch, &b)) return rc;
+    if (const int rc = batch_queue(run, m, &b)) return rc;
     if (const int rc = batch_harvest(run, b)) return rc;
   }
   return run.done;
@@ -212,7 +217,7 @@ int rgpu_run_steps_monitored(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, d
   if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, "run_steps_monitored: single-domain contexts only (a slab holds a part of the box)");
   if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_monitored: nsteps is negative");
   if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_monitored: every must be at least 1");
-  const MonRun M = {every, false, (size_t)RGPU_MON_NQ, mon_n, mon_step, mon_t, mon, "run_steps_monitored"};
+  const MonRun M = {every, {MON_MONITOR, 0, 0}, (size_t)RGPU_MON_NQ, mon_n, mon_step, mon_t, mon, "run_steps_monitored"};
   LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
   return run_steps_impl(run);
 }
@@ -230,7 +235,23 @@ int rgpu_run_steps_monitored_planes(rgpu_ctx* c, int nsteps, double tEnd, int* n
   if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: nsteps is negative");
   if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: every must be at least 1");
   if (!monitor_planes_scratch_fits(c)) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: no scratch for the partial sums");
-  const MonRun M = {every, true, monp_sample_doubles(c->g), mon_n, mon_step, mon_t, mon, "run_steps_monitored_planes"};
+  const MonRun M = {every, {MON_PLANES, 0, 0}, monp_sample_doubles(c->g), mon_n, mon_step, mon_t, mon, "run_steps_monitored_planes"};
+  LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
+  return run_steps_impl(run);
+}
+
+long rgpu_map_batch_samples(rgpu_ctx* c) { return c ? c->monm_samples : 0; }
+
+int rgpu_run_steps_mapped(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int every,
+                          int nmaps, const rgpu_map_spec* specs, int* mon_n, int* mon_step, double* mon_t, double* maps) {
+  RG_CHECK_CTX(c);
+  if (mon_n) *mon_n = 0;
+  if (!nStep || !t || !dt || !specs || !mon_n || !mon_step || !mon_t || !maps) return fail(c, RGPU_EINVAL, "run_steps_mapped: null pointer");
+  if (const int rc = maps_refusal(c, "run_steps_mapped", nmaps, specs)) return rc;
+  if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_mapped: nsteps is negative");
+  if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_mapped: every must be at least 1");
+  const MonSample S = {MON_MAPS, nmaps, specs};
+  const MonRun M = {every, S, monitor_sample_doubles(c, S), mon_n, mon_step, mon_t, maps, "run_steps_mapped"};
   LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
   return run_steps_impl(run);
 }

@@ -19,3 +19,6 @@
 #include "monitor_profile.h"
 // the gfx950 kernels of the plane monitor exist (api/monitor.h: without this macro it runs the flat functors)
 #define RGPU_TILED_MONITOR_PROFILE 1
+#include "monitor_maps.h"
+// the gfx950 kernels of the map monitor exist (api/monitor.h: without this macro it runs the flat functor)
+#define RGPU_TILED_MONITOR_MAPS 1

@@ -793,6 +793,84 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
   }
   std::vector<int> mon_step;
   std::vector<double> mon_t, mon_v;
+  // [maps] enabled=yes every=N map0=z:16 map1=y:0-24 map2=x:all ... (up to map7, numbered from 0 without a gap): pictures of a 3D
+  // single-domain run (include/rgpu.h, "map monitors") after every step that brings nStep to a multiple of `every`.  A map is
+  // axis:index (a slice), axis:lo-hi (the cells lo .. hi - 1 summed along the axis) or axis:all.  Each sample of each map is one file
+  // <outputDir>/<outputPrefix>_map<m>_<step, 7 digits>.npy -- NumPy format 1.0, '<f8', C order, shape (12, nv, nu), the channels
+  // RGPU_MAP_NAMES -- and one line "step t map axis lo hi file" of <outputPrefix>_maps.txt, t with 17 significant digits.  Driven as
+  // the [monitor] block drives its run: the quiet turns go through rgpu_run_steps_mapped (the maps taken on the device inside the
+  // device-clock batches); with a history file the loop is cut at the sampling steps and takes the maps by rgpu_state_maps -- the
+  // same doubles either way.  With [monitor] on as well the maps take the batches and the monitor rows come from the direct calls
+  // (the same rows: a batch serves one consumer).  Not for z-slab, hooked or 2D runs.
+  const bool mapsEnabled = cfg_.get_bool("maps", "enabled", false);
+  const int maps_every = mapsEnabled ? (int)cfg_.get_integer("maps", "every", 10) : 0;
+  if (mapsEnabled && maps_every < 1) throw std::runtime_error("[maps] every must be at least 1");
+  bool noted_maps = false;
+  if (mapsEnabled && (slab() || hooked_ || p_.nz_global == 1)) note_once(&noted_maps, p_.nz_global == 1 ? "2D run: the map files are not written" : "z-slab run: the map files are not written");
+  std::vector<rgpu_map_spec> map_specs;
+  std::vector<size_t> map_at(1, 0);   // map m of a sample begins at map_at[m]; map_at.back(): the doubles of a sample
+  if (mapsEnabled && !slab() && !hooked_ && p_.nz_global != 1) {
+    for (int m = 0; m < RGPU_MAP_MAX; ++m) {
+      const std::string key = "map" + std::to_string(m), text = cfg_.get_string("maps", key, "");
+      if (text.empty()) break;
+      const int n[3] = {p_.nx, p_.ny, p_.nz};
+      rgpu_map_spec sp = {-1, 0, 0};
+      if (text.size() > 2 && text[1] == ':') sp.axis = text[0] == 'x' ? 0 : text[0] == 'y' ? 1 : text[0] == 'z' ? 2 : -1;
+      const std::string range = sp.axis >= 0 ? text.substr(2) : std::string();
+      char* end = 0;
+      if (range == "all") { sp.lo = 0; sp.hi = n[sp.axis]; }
+      else if (!range.empty()) {
+        sp.lo = (int)std::strtol(range.c_str(), &end, 10);
+        sp.hi = sp.lo + 1;
+        if (*end == '-' && end != range.c_str()) { const char* second = end + 1; sp.hi = (int)std::strtol(second, &end, 10); if (end == second) sp.axis = -1; }
+        if (*end != 0) sp.axis = -1;
+      }
+      const size_t doubles = rgpu_map_doubles(ctx_, &sp);
+      if (doubles == 0) throw std::runtime_error("[maps] " + key + "=" + text + ": expected x|y|z followed by :index, :lo-hi (lo inclusive, hi exclusive) or :all, inside the box");
+      map_specs.push_back(sp);
+      map_at.push_back(map_at.back() + doubles);
+    }
+  }
+  const bool maps_on = !map_specs.empty();
+  const std::string maps_list = rs_.outputDir + "/" + rs_.outputPrefix + "_maps.txt";
+  // n samples of all maps: the .npy files and their lines in the list
+  const auto maps_files = [&](int n, const int* step, const double* t, const double* v) {
+    std::ofstream list(maps_list.c_str(), std::ios::app);
+    if (!list) throw std::runtime_error("cannot write " + maps_list);
+    char num[64];
+    for (int k = 0; k < n; ++k)
+      for (size_t m = 0; m < map_specs.size(); ++m) {
+        const rgpu_map_spec& sp = map_specs[m];
+        const int nu = sp.axis == 0 ? p_.ny : p_.nx, nv = sp.axis == 2 ? p_.ny : p_.nz;
+        std::snprintf(num, sizeof(num), "_map%d_%07d.npy", (int)m, step[k]);
+        const std::string name = rs_.outputPrefix + num, path = rs_.outputDir + "/" + name;
+        // NumPy format 1.0: magic, version, the length of the header (little endian), the header padded with spaces to a multiple of 64
+        std::string head = "{'descr': '<f8', 'fortran_order': False, 'shape': (" + std::to_string(RGPU_MAP_NQ) + ", " + std::to_string(nv) + ", " + std::to_string(nu) + "), }";
+        head.append(63 - (10 + head.size()) % 64, ' ');
+        head += "\n";
+        std::ofstream f(path.c_str(), std::ios::binary | std::ios::trunc);
+        const char magic[10] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0, (char)(head.size() & 0xff), (char)(head.size() >> 8)};
+        f.write(magic, 10);
+        f.write(head.data(), (std::streamsize)head.size());
+        f.write(reinterpret_cast<const char*>(v + (size_t)k * map_at.back() + map_at[m]), (std::streamsize)((map_at[m + 1] - map_at[m]) * sizeof(double)));
+        if (!f) throw std::runtime_error("cannot write " + path);
+        std::snprintf(num, sizeof(num), " %.17g", t[k]);
+        list << step[k] << num << " " << m << " " << "xyz"[sp.axis] << " " << sp.lo << " " << sp.hi << " " << name << "\n";
+      }
+  };
+  std::vector<double> maps_v;
+  std::vector<int> maps_step;
+  std::vector<double> maps_t;
+  const auto maps_direct = [&](int n) {   // the maps of the current state U[n % 2]
+    maps_v.resize(std::max(maps_v.size(), map_at.back()));
+    check(rgpu_state_maps(ctx_, n % 2, (int)map_specs.size(), map_specs.data(), maps_v.data()), "state_maps");
+    maps_files(1, &n, &totalTime_, maps_v.data());
+  };
+  if (maps_on && !(totalTime_ > 0)) {   // the start of a run
+    std::ofstream f(maps_list.c_str(), std::ios::trunc);
+    if (!f) throw std::runtime_error("cannot write " + maps_list);
+    f << "# nStep totalTime map axis lo hi file\n";
+  }
   const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   while (totalTime_ < rs_.tEnd && nStep < rs_.nStepmax) {
     if (rs_.nLog > 0 && (nStep % rs_.nLog) == 0 && p_.slab_rank == 0)
@@ -823,10 +901,21 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
       if (rs_.nLog > 0 && rs_.nLog - nStep % rs_.nLog < quiet) quiet = rs_.nLog - nStep % rs_.nLog;
       if (rs_.nOutput > 0 && rs_.nOutput - nStep % rs_.nOutput < quiet) quiet = rs_.nOutput - nStep % rs_.nOutput;
     }
-    const bool monitor_batched = monitor_on && !historyEnabled && quiet > 1;
+    // a batch serves one consumer: where the maps take it, the monitor rows come from the direct calls
+    const bool maps_batched = maps_on && !historyEnabled && quiet > 1;
+    const bool monitor_batched = monitor_on && !historyEnabled && quiet > 1 && !maps_batched;
     if (monitor_on && !monitor_batched && mon_every - nStep % mon_every < quiet) quiet = mon_every - nStep % mon_every;   // the direct call follows
+    if (maps_on && !maps_batched && maps_every - nStep % maps_every < quiet) quiet = maps_every - nStep % maps_every;      // the direct call follows
     const int nStep_before = nStep;
-    if (monitor_batched && planes_on) {
+    if (maps_batched) {
+      int mn = 0;
+      const size_t cap = (size_t)(quiet / maps_every + 1);
+      if (maps_step.size() < cap) { maps_step.resize(cap); maps_t.resize(cap); }
+      if (maps_v.size() < cap * map_at.back()) maps_v.resize(cap * map_at.back());
+      const int rc = rgpu_run_steps_mapped(ctx_, quiet, rs_.tEnd, &nStep, &totalTime_, &dt, 0, maps_every, (int)map_specs.size(), map_specs.data(), &mn, maps_step.data(), maps_t.data(), maps_v.data());
+      maps_files(mn, maps_step.data(), maps_t.data(), maps_v.data());
+      if (rc < 0) check(rc, "run_steps_mapped");
+    } else if (monitor_batched && planes_on) {
       int mn = 0;
       const size_t cap = (size_t)(quiet / mon_every + 1);
       if (mon_step.size() < cap) { mon_step.resize(cap); mon_t.resize(cap); }
@@ -859,6 +948,7 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
       oneStepIntegration(nStep, totalTime_, dt);
     }
     if (monitor_on && !monitor_batched && nStep > nStep_before && nStep % mon_every == 0) monitor_direct(nStep);
+    if (maps_on && !maps_batched && nStep > nStep_before && nStep % maps_every == 0) maps_direct(nStep);
   }
   check(rgpu_synchronize(ctx_), "synchronize");
   if (hooked_) hook_check(hooks_.barrier(hooks_.self), "barrier");

@@ -19,6 +19,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # the series out of run_steps_monitored (of a Solver, of one member of an Ensemble): step numbers [n], times [n], values [n, 10]
 # (columns _capi.MON_NAMES); out of run_steps_monitored_planes: values [n, nz, 16] (columns _capi.MONP_NAMES)
 MonitorSeries = collections.namedtuple("MonitorSeries", "step t values")
+# the series out of run_steps_mapped: step numbers [n], times [n], and per spec an array [n, 12, nv, nu] (channels _capi.MAP_NAMES)
+MapSeries = collections.namedtuple("MapSeries", "step t maps")
 
 
 def lib_path(arithmetic=None):
@@ -310,6 +312,50 @@ class Solver:
             self._chk(done, "run_steps_monitored_planes")
         self.dt_log = [log[i] for i in range(done)]
         return done, self.monitor_planes_series
+
+    def _map_specs(self, specs):
+        """specs, each (axis, lo, hi) with the axis 0 / 1 / 2 or "x" / "y" / "z" -> (the C array, the shape [12, nv, nu] of each map)"""
+        n = (self.p.nx, self.p.ny, self.p.nz)
+        arr = (_capi.RgpuMapSpec * max(len(specs), 1))()
+        shapes = []
+        for m, (axis, lo, hi) in enumerate(specs):
+            a = "xyz".index(axis) if isinstance(axis, str) else int(axis)
+            arr[m].axis, arr[m].lo, arr[m].hi = a, int(lo), int(hi)
+            shapes.append((_capi.MAP_NQ,) + {0: (n[2], n[1]), 1: (n[2], n[0]), 2: (n[1], n[0])}.get(a, (0, 0)))
+        return arr, shapes
+
+    def state_maps(self, specs, parity=None):
+        """maps of U[parity] (default: nStep % 2) of a 3D state: a list, per spec (axis, lo, hi), of ndarrays [12, nv, nu] -- the
+        channels _capi.MAP_NAMES of every pixel summed over the cells lo .. hi - 1 along the axis ("x" / "y" / "z" or 0 / 1 / 2), a
+        slice where hi == lo + 1 (rgpu_state_maps; include/rgpu.h, "map monitors")"""
+        arr, shapes = self._map_specs(specs)
+        out = np.zeros(max(sum(int(np.prod(s)) for s in shapes), 1))
+        par = self.nStep % 2 if parity is None else int(parity)
+        self._chk(self.lib.rgpu_state_maps(self.ctx, par, len(specs), arr, out.ctypes.data_as(_capi.c_double_p)), "state_maps")
+        cuts = np.cumsum([0] + [int(np.prod(s)) for s in shapes])
+        return [out[cuts[m]:cuts[m + 1]].reshape(shapes[m]).copy() for m in range(len(specs))]
+
+    def run_steps_mapped(self, nsteps, every, specs, tEnd=float("inf")):
+        """run_steps with a sample of the maps `specs` after every step that brings nStep to a multiple of `every`
+        (rgpu_run_steps_mapped: inside the device-clock batches the maps are taken on the device, one read-back per batch).  Returns
+        (done, MapSeries): the steps done and the samples of this call -- .step [n], .t [n] (the time after that step), .maps a list
+        per spec of [n, 12, nv, nu] (_capi.MAP_NAMES)"""
+        arr, shapes = self._map_specs(specs)
+        sizes = [int(np.prod(s)) for s in shapes]
+        cap = max(int(nsteps), 0) // max(int(every), 1) + 1
+        n, t, d, mn = C.c_int(self.nStep), C.c_double(self.totalTime), C.c_double(self.dt), C.c_int(0)
+        log = (C.c_double * max(int(nsteps), 1))()
+        mstep, mt, mv = np.zeros(cap, dtype=np.intc), np.zeros(cap), np.empty((cap, max(sum(sizes), 1)))   # (mv: only the samples written are read)
+        done = self.lib.rgpu_run_steps_mapped(self.ctx, int(nsteps), float(tEnd), C.byref(n), C.byref(t), C.byref(d), log, int(every), len(specs), arr, C.byref(mn),
+                                              mstep.ctypes.data_as(C.POINTER(C.c_int)), mt.ctypes.data_as(_capi.c_double_p), mv.ctypes.data_as(_capi.c_double_p))
+        k = mn.value
+        self.nStep, self.totalTime, self.dt = n.value, t.value, d.value   # (they describe the steps that ran, also when the call failed)
+        cuts = np.cumsum([0] + sizes)
+        self.map_series = MapSeries(mstep[:k].astype(int), mt[:k].copy(), [mv[:k, cuts[m]:cuts[m + 1]].reshape((k,) + shapes[m]).copy() for m in range(len(specs))])
+        if done < 0:
+            self._chk(done, "run_steps_mapped")
+        self.dt_log = [log[i] for i in range(done)]
+        return done, self.map_series
 
     def history_turbulence(self, nStep=None):
         """history_turbulence (MHDRunBase.cpp:3626-3810) reduced on the device: the 18 columns after totalTime and dt"""
