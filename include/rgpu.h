@@ -727,6 +727,76 @@ int rgpu_run_steps_mapped(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, doub
                           double* maps /* [cap][sum of rgpu_map_doubles] */);
 long rgpu_map_batch_samples(rgpu_ctx* c);
 
+/* ---- PDF monitors: histograms of a 3D state, counted on the device ---------------------------------------------------------------------
+ * The distribution is the fourth shape of the family: the density PDF of a turbulent box, the PDF of |B|, of the magnetic energy or of
+ * |div B| in an MRI run, and the joint PDFs -- rho against eint, rho against emag.  A PDF is a table of 64-bit COUNTS over the nx ny nz
+ * interior cells of U[parity] of a single-domain 3D context as the array stands, hydro or MHD, shearing box included.  No ghost fill
+ * is done; the high faces of the last interior row, column and plane come from the first ghost layer, as for the monitors.  Counts
+ * are integers and do not depend on the order of arrival: a table depends on the state and the spec only -- not on the library, on
+ * which kernel variant ran, on the grid size, or on whether and where in a batch the sample is taken.
+ * Channels, in the order of RGPU_PDF_NAMES: channel q < 12 of a cell is column {0, 1, 2, 3, 4, 5, 6, 8, 10, 11, 12, 9}[q] of the plane
+ * monitor's per-cell terms above (rho = its "mass" term, eint = its "min_eint" term (E - ekin) - emag, absdivb = its "max_absdivb"
+ * term): the same operations in the same order, no FMA contraction in either library (csrc/kernels_monitor_pdf.h picks them, it
+ * restates nothing).  Channel 12: v2 = (ekin + ekin) / rho, the speed squared, from those terms, not contracted.  For a hydro state
+ * emag, bx, by, bz and absdivb are exactly +0.0; they may be histogrammed and land in `under` or in the bin that holds 0.
+ * An axis: { channel; scale; nbins; sub; lo; hi }.  A value x of the channel falls into one of nbins + 3 classes: the bins 0 .. nbins - 1,
+ * then under (nbins), over (nbins + 1) and nan (nbins + 2).  x != x gives nan, tested first.  Otherwise
+ *   scale == 0, linear: finite lo < hi and nbins >= 1 (sub is ignored).  x < lo: under.  x >= hi: over.  Else the bin is the integer
+ *       part of (x - lo) * inv, at most nbins - 1, where inv = (double)nbins / (hi - lo) is computed once on the host; the subtraction
+ *       and the product are IEEE operations, not contracted, in both libraries.
+ *   scale == 1, octave bins on |x|, each octave cut into 2^sub sub-bins of equal width; no logarithm is evaluated.  lo and hi are
+ *       normal powers of two, lo < hi; 0 <= sub <= 6; nbins == (log2 hi - log2 lo) << sub, anything else is refused.  |x| < lo:
+ *       under (zeros and subnormals too).  |x| >= hi: over (infinity too).  Else the bin is (bits(|x|) >> (52 - sub)) - (bits(lo)
+ *       >> (52 - sub)), integer arithmetic on the IEEE representation.  Bin b is [lo 2^o (1 + r / 2^sub), lo 2^o (1 + (r + 1) / 2^sub))
+ *       with o = b >> sub, r = b mod 2^sub: the edges are exactly representable, so a true log-PDF follows from the counts and the
+ *       known widths.
+ * A spec: { a; b }.  b.nbins == 0: the 1D histogram of a, a.nbins + 3 words in class order (b is not looked at).  Else the joint
+ * table, (a.nbins + 3) x (b.nbins + 3) words, the word of a cell at ia * (b.nbins + 3) + ib; the tail classes are its last three rows
+ * and columns.  Identities: the words of every spec sum to nx ny nz; the sum of a joint table over ib is the 1D histogram of a, word
+ * for word.  (tests/monitor_pdf_checks.py is this definition in numpy.)
+ *
+ *   rgpu_pdf_words         the words of *spec; 0 for a spec that is refused (a bad axis, more than RGPU_PDF_MAX_WORDS words, NULL).
+ *   rgpu_state_pdfs        npdfs tables of U[parity], one after another in `out` (table m at the sum of rgpu_pdf_words of the specs
+ *                          before it).  The state is read ONCE however many specs the call has -- hence the shared word budget,
+ *                          RGPU_PDF_MAX_WORDS for all specs of a call together: the counts of a workgroup are kept in LDS.  Reads
+ *                          the state only: ghost cells, CFL slots and what the context knows about them stay as they are.  Two
+ *                          launches (csrc/hip/monitor_pdf.h), partial counts in the flux array, which is dead between two steps.
+ *                          Synchronises.
+ *   rgpu_run_steps_pdfs    rgpu_run_steps_log (same states, same dt sequence, same return value) plus sampling, with the semantics of
+ *                          rgpu_run_steps_mapped word for word: a sample (all npdfs tables) after each step that brings *nStep to a
+ *                          multiple of `every`; *mon_n = the samples of this call (<= cap = nsteps / every + 1); sample k:
+ *                          mon_step[k], mon_t[k] the host-accumulated *t after that step, pdfs + k * W (W = the sum of
+ *                          rgpu_pdf_words over the specs) what rgpu_state_pdfs gives on that state, word for word.  A step that
+ *                          reaches tEnd is sampled if it qualifies, nothing is sampled after a stop; *mon_n counts only samples
+ *                          whose values were written.  A run cut into calls gives the series of one call.  dt_log may be NULL.
+ *                          Where the context takes its time step from the device (rgpu_device_time_step_ready) the kernels of a
+ *                          sample are queued behind the last kernel of each qualifying step, return in their first instructions when
+ *                          the step's clock record says stop, and store to a device log that is copied back once per batch with the
+ *                          clock records: no synchronisation inside a batch, no zeroing of the log.  Everywhere else (first steps,
+ *                          gravity, the dissipative stage, forcing, phase timers, option "step_clock" = 0) the call is the literal
+ *                          loop: rgpu_one_step_integration, then rgpu_state_pdfs.  The log has RGPU_CLOCK_BATCH / every + 1 slots
+ *                          (a sample is at most 128 KiB), is allocated by the first call that needs it, grown between batches if a
+ *                          later call needs more, freed with the context, and is not part of rgpu_device_bytes.
+ *   rgpu_pdf_batch_samples how many samples this context has queued on the device inside its batches so far (0 where every call
+ *                          took the literal loop).  These calls leave the other monitors' counters alone.
+ *   Errors (nothing has run, *mon_n == 0): RGPU_EUNSUPPORTED for a 2D context ("3D" in the message); RGPU_EINVAL for a slab context
+ *                          (slab_count > 1), a NULL pointer among nStep, t, dt, specs, mon_n, mon_step, mon_t, pdfs / out, nsteps
+ *                          < 0, every < 1 ("every" in the message), npdfs outside 1 .. RGPU_PDF_MAX, a bad axis -- channel, scale,
+ *                          range, the power-of-two rule, nbins, sub (the message names the spec, "pdf 1: ...") -- more than
+ *                          RGPU_PDF_MAX_WORDS words in all, or a flux array too small for one workgroup's counts. */
+#define RGPU_PDF_NQ 13
+#define RGPU_PDF_NAMES "rho mx my mz E ekin emag eint bx by bz absdivb v2"   /* the RGPU_PDF_NQ channels, in order */
+#define RGPU_PDF_MAX 8                                                      /* specs per call */
+#define RGPU_PDF_MAX_WORDS 16384                                            /* words of all specs of a call together */
+typedef struct { int channel; int scale; int nbins; int sub; double lo; double hi; } rgpu_pdf_axis;
+typedef struct { rgpu_pdf_axis a, b; } rgpu_pdf_spec;   /* b.nbins == 0: a 1D histogram of a; else the joint one */
+size_t rgpu_pdf_words(const rgpu_pdf_spec* spec);
+int rgpu_state_pdfs(rgpu_ctx* c, int parity, int npdfs, const rgpu_pdf_spec* specs, unsigned long long* out);
+int rgpu_run_steps_pdfs(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log,
+                        int every, int npdfs, const rgpu_pdf_spec* specs, int* mon_n, int* mon_step /* [cap] */, double* mon_t /* [cap] */,
+                        unsigned long long* pdfs /* [cap][sum of rgpu_pdf_words] */);
+long rgpu_pdf_batch_samples(rgpu_ctx* c);
+
 /* Self-test of the device arithmetic the parity contract rests on: for n operand pairs computes on the device
  *   quot[i]  = rg_div(num[i], rg_recip(den[i]))   the shared-reciprocal division of csrc/hip/rg_backend.h
  *   quot2[i] = num[i] / den[i]                    the compiler's IEEE division
@@ -771,8 +841,10 @@ int rgpu_selftest_alfven(const rgpu_params* p, int n, const double* states36, do
  *                       parameter scan), even when all sets are equal: the table path and the by-value path on one workload
  *   "map_log_kib" (262144) byte budget, in KiB, of the device log of the maps a batch of rgpu_run_steps_mapped samples ("map monitors")
  *   "map_x_tiled" (-1)  which kernel sums a map along x: -1 by the thickness of the range, 0 the direct one, 1 the tiled one (the same bits)
+ *   "pdf_replicas" (-1) copies of the LDS table of counts the PDF monitor's kernel keeps: -1 automatic, n forces the count (the same words)
+ *   "pdf_groups" (-1)   workgroups of that kernel: -1 automatic, n forces the grid size (the same words)
  * rgpu_set_option returns the previous value (-1: unknown name; the options above are never negative except "as created" and the
- * default of "map_x_tiled"). */
+ * defaults of "map_x_tiled", "pdf_replicas" and "pdf_groups"). */
 int rgpu_set_option(const char* name, int value);
 int rgpu_get_option(const char* name);
 

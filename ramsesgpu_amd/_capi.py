@@ -17,6 +17,11 @@ MONP_NQ = len(MONP_NAMES)
 MAP_NAMES = ("rho", "mx", "my", "mz", "E", "ekin", "emag", "eint", "bx", "by", "bz", "rho2")
 MAP_NQ = len(MAP_NAMES)
 MAP_MAX = 8
+# the channels of a PDF (rgpu_state_pdfs, rgpu_run_steps_pdfs): RGPU_PDF_NQ = 13, columns 0 1 2 3 4 5 6 8 10 11 12 9 of the plane monitor's terms, then v2
+PDF_NAMES = ("rho", "mx", "my", "mz", "E", "ekin", "emag", "eint", "bx", "by", "bz", "absdivb", "v2")
+PDF_NQ = len(PDF_NAMES)
+PDF_MAX = 8
+PDF_MAX_WORDS = 16384
 T_NAMES = ["boundaries", "prim", "elec", "trace", "flux", "emf", "update", "shear", "dt", "dissipative", "sweep"]
 
 
@@ -78,6 +83,16 @@ c_double_p = C.POINTER(C.c_double)
 class RgpuMapSpec(C.Structure):
     """rgpu_map_spec: axis 0 = x, 1 = y, 2 = z, the direction summed over; [lo, hi) in interior indices along it"""
     _fields_ = [("axis", C.c_int), ("lo", C.c_int), ("hi", C.c_int)]
+
+
+class RgpuPdfAxis(C.Structure):
+    """rgpu_pdf_axis: the channel; scale 0 linear bins on [lo, hi), 1 octave bins on |x| with 2^sub sub-bins each, lo and hi powers of two"""
+    _fields_ = [("channel", C.c_int), ("scale", C.c_int), ("nbins", C.c_int), ("sub", C.c_int), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class RgpuPdfSpec(C.Structure):
+    """rgpu_pdf_spec: b.nbins == 0: the 1D histogram of a; else the joint table [a.nbins + 3][b.nbins + 3]"""
+    _fields_ = [("a", RgpuPdfAxis), ("b", RgpuPdfAxis)]
 
 
 def declare_host_api(lib):
@@ -249,6 +264,17 @@ def declare_device_api(lib):
                                               C.c_int, C.POINTER(RgpuMapSpec), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]
         lib.rgpu_map_batch_samples.restype = C.c_long
         lib.rgpu_map_batch_samples.argtypes = [ctx]
+    if hasattr(lib, "rgpu_state_pdfs"):   # (absent from an older build of the library)
+        c_u64_p = C.POINTER(C.c_ulonglong)
+        lib.rgpu_pdf_words.restype = C.c_size_t
+        lib.rgpu_pdf_words.argtypes = [C.POINTER(RgpuPdfSpec)]
+        lib.rgpu_state_pdfs.restype = C.c_int
+        lib.rgpu_state_pdfs.argtypes = [ctx, C.c_int, C.c_int, C.POINTER(RgpuPdfSpec), c_u64_p]
+        lib.rgpu_run_steps_pdfs.restype = C.c_int
+        lib.rgpu_run_steps_pdfs.argtypes = [ctx, C.c_int, C.c_double, C.POINTER(C.c_int), c_double_p, c_double_p, c_double_p, C.c_int,
+                                            C.c_int, C.POINTER(RgpuPdfSpec), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_u64_p]
+        lib.rgpu_pdf_batch_samples.restype = C.c_long
+        lib.rgpu_pdf_batch_samples.argtypes = [ctx]
     return lib
 
 
@@ -301,4 +327,5 @@ DECLARED_SYMBOLS = [
     "rgpu_state_monitor3d", "rgpu_run_steps_monitored", "rgpu_monitor_batch_samples",
     "rgpu_state_monitor_planes", "rgpu_run_steps_monitored_planes", "rgpu_monitor_planes_batch_samples",
     "rgpu_map_doubles", "rgpu_state_maps", "rgpu_run_steps_mapped", "rgpu_map_batch_samples",
+    "rgpu_pdf_words", "rgpu_state_pdfs", "rgpu_run_steps_pdfs", "rgpu_pdf_batch_samples",
 ]

@@ -109,6 +109,12 @@ struct rgpu_ctx {
   DeviceMirror<double> monm;
   size_t monm_doubles = 0;
   long monm_samples = 0;        // map samples queued on the device inside batches so far (rgpu_map_batch_samples)
+  // the PDFs (kernels_monitor_pdf.h; rgpu_state_pdfs, rgpu_run_steps_pdfs): the device buffer the fold kernel of a sample stores to
+  // -- one sample taken outside a batch at its head, or the samples of a batch.  Its words are 64-bit counts: the log is typed as
+  // the others are and only ever copied, the kernels get it as unsigned long long.  monh_words words, grown by a call that needs more
+  DeviceMirror<double> monh;
+  size_t monh_words = 0;
+  long monh_samples = 0;        // PDF samples queued on the device inside batches so far (rgpu_pdf_batch_samples)
   // fused 2D steps: the clock is folded into the step kernel itself (step_clock_rec.h: ClockFold) over three rotating slot arrays;
   // d_red always points at the array that holds the maxima of the current state
   unsigned long long* d_red_base = 0;   // 3 x RG_DT_SLOTS

@@ -314,6 +314,8 @@ size_t rgpu_map_doubles(rgpu_ctx* c, const rgpu_map_spec* spec) {
   if (!c || !spec || !c->U[0] || !c->g.three_d || c->p.slab_count > 1 || !map_spec_error(c, *spec).empty()) return 0;
   return map_doubles(c, *spec);
 }
+int rgpu_state_pdfs(rgpu_ctx* c, int parity, int npdfs, const rgpu_pdf_spec* specs, unsigned long long* out) { return state_pdfs(c, parity, npdfs, specs, out); }
+size_t rgpu_pdf_words(const rgpu_pdf_spec* spec) { return spec && pdf_spec_error(*spec).empty() ? pdf_spec_words(*spec) : 0; }
 
 double rgpu_compute_dt(rgpu_ctx* c, int useU) {
   double v = 0;

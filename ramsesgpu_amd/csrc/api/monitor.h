@@ -1,7 +1,8 @@
 // api/monitor.h -- the monitor of a lone context on the host side (kernels_monitor.h): scratch extent and launches of one sample, for
 // rgpu_state_monitor (2D), rgpu_state_monitor3d and a sample queued inside a device-clock batch (rgpu_run_steps_monitored); the same for
 // the plane monitor (kernels_monitor_planes.h: rgpu_state_monitor_planes, rgpu_run_steps_monitored_planes) and for the map monitor
-// (kernels_monitor_maps.h: rgpu_state_maps, rgpu_run_steps_mapped).  See api/ctx.h.
+// (kernels_monitor_maps.h: rgpu_state_maps, rgpu_run_steps_mapped) and for the PDF monitor (kernels_monitor_pdf.h: rgpu_state_pdfs,
+// rgpu_run_steps_pdfs).  See api/ctx.h.
 #pragma once
 namespace {
 // One route for either dimension, a 2D state being a volume of one plane.  Everything on the device, the sum over the planes included,
@@ -149,26 +150,134 @@ int state_maps(rgpu_ctx* c, int parity, int nmaps, const rgpu_map_spec* specs, d
   return RGPU_OK;
 }
 
-// ---- the samples of a batch: of the monitor, of the plane monitor, or of the map monitor ------------------------------------------
-// which sample a call takes (and, for maps, of what)
-enum MonWhat { MON_MONITOR, MON_PLANES, MON_MAPS };
-struct MonSample { MonWhat what; int nmaps; const rgpu_map_spec* specs; };
+// ---- the PDF monitor (kernels_monitor_pdf.h): the same consumer with a fourth sample, the tables of counts of npdfs specs ------------
+static_assert(PDF_NQ == RGPU_PDF_NQ && PDF_MAX == RGPU_PDF_MAX && PDF_MAX_WORDS == RGPU_PDF_MAX_WORDS, "include/rgpu.h states the channels and the budgets of the PDFs");
+// whether x is a normal power of two; *e: its biased exponent
+bool pdf_pow2(double x, int* e) {
+  unsigned long long u;
+  std::memcpy(&u, &x, sizeof(u));
+  *e = (int)(u >> 52);   // (with the sign bit: a negative number fails the range test)
+  return (u & ((1ull << 52) - 1)) == 0 && *e >= 1 && *e <= 2046;
+}
+// "" for an axis that can be taken, else what is wrong with it
+std::string pdf_axis_error(const rgpu_pdf_axis& a) {
+  if (a.channel < 0 || a.channel >= RGPU_PDF_NQ) return "channel must be 0 .. " + std::to_string(RGPU_PDF_NQ - 1);
+  if (a.nbins < 1 || a.nbins > RGPU_PDF_MAX_WORDS) return "nbins must be at least 1 (and within the word budget)";
+  if (a.scale == 0) return std::isfinite(a.lo) && std::isfinite(a.hi) && a.lo < a.hi ? "" : "a linear range must be finite with lo < hi";
+  if (a.scale != 1) return "scale must be 0 (linear) or 1 (octave bins)";
+  int elo = 0, ehi = 0;
+  if (!pdf_pow2(a.lo, &elo) || !pdf_pow2(a.hi, &ehi) || !(a.lo < a.hi)) return "an octave range must have normal powers of two lo < hi";
+  if (a.sub < 0 || a.sub > 6) return "sub must be 0 .. 6";
+  if (a.nbins != (ehi - elo) << a.sub) return "nbins must be (log2 hi - log2 lo) << sub = " + std::to_string((ehi - elo) << a.sub);
+  return "";
+}
+// (of a spec whose axes can be taken)
+size_t pdf_spec_words(const rgpu_pdf_spec& s) { return (size_t)(s.a.nbins + 3) * (s.b.nbins == 0 ? (size_t)1 : (size_t)(s.b.nbins + 3)); }
+std::string pdf_spec_error(const rgpu_pdf_spec& s) {
+  std::string why = pdf_axis_error(s.a);
+  if (!why.empty()) return "axis a: " + why;
+  if (s.b.nbins != 0 && !(why = pdf_axis_error(s.b)).empty()) return "axis b: " + why;
+  if (pdf_spec_words(s) > (size_t)RGPU_PDF_MAX_WORDS) return "more than " + std::to_string(RGPU_PDF_MAX_WORDS) + " words";
+  return "";
+}
+PdfAxis pdf_axis_make(const rgpu_pdf_axis& a) {
+  PdfAxis d = {a.channel, a.scale, a.nbins, 0, a.lo, a.hi, 0.0, 0ull};
+  if (a.scale == 0) d.inv = (double)a.nbins / (a.hi - a.lo);
+  else {
+    d.shift = 52 - a.sub;
+    std::memcpy(&d.key0, &a.lo, sizeof(d.key0));
+    d.key0 >>= d.shift;
+  }
+  return d;
+}
+// the slabs of one workgroup's counts the flux array holds (u32 words, two to a double)
+size_t pdf_scratch_groups(const rgpu_ctx* c, const PdfSet& S) { return c->F ? (size_t)c->g.fN * plan_for(c->p).f * 2 / S.words : 0; }
+// what rgpu_state_pdfs and rgpu_run_steps_pdfs refuse alike, in this order; 0: the tables can be taken, and *S is what the kernels read
+int pdfs_refusal(rgpu_ctx* c, const std::string& who, int npdfs, const rgpu_pdf_spec* specs, PdfSet* S) {
+  if (!c->U[0]) return fail(c, RGPU_EINVAL, who + ": context without state");
+  if (!c->g.three_d) return fail(c, RGPU_EUNSUPPORTED, who + ": 3D contexts only");
+  if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, who + ": single-domain contexts only (a slab holds a part of the box)");
+  if (npdfs < 1 || npdfs > RGPU_PDF_MAX) return fail(c, RGPU_EINVAL, who + ": npdfs must be 1 .. " + std::to_string(RGPU_PDF_MAX));
+  size_t words = 0;
+  for (int m = 0; m < npdfs; ++m) {
+    const std::string why = pdf_spec_error(specs[m]);
+    if (!why.empty()) return fail(c, RGPU_EINVAL, who + ": pdf " + std::to_string(m) + ": " + why);
+    PdfTable& t = S->t[m];
+    t.a = pdf_axis_make(specs[m].a);
+    t.joint = specs[m].b.nbins != 0;
+    t.b = t.joint ? pdf_axis_make(specs[m].b) : t.a;
+    t.base = (unsigned)words;
+    t.pitch = t.joint ? (unsigned)(specs[m].b.nbins + 3) : 1u;
+    words += pdf_spec_words(specs[m]);
+  }
+  if (words > (size_t)RGPU_PDF_MAX_WORDS) return fail(c, RGPU_EINVAL, who + ": the specs have " + std::to_string(words) + " words together, more than " + std::to_string(RGPU_PDF_MAX_WORDS));
+  S->n = npdfs;
+  S->words = (unsigned)words;
+  if (pdf_scratch_groups(c, *S) < 1) return fail(c, RGPU_EINVAL, who + ": no scratch for the partial counts");
+  return RGPU_OK;
+}
+// the device buffer the samples are stored to, at least `words` long: grown between two batches or two calls, when nothing is in
+// flight.  Not zeroed: every word that is read was stored by the fold kernel.  != 0: it is not there
+int pdf_log_reserve(rgpu_ctx* c, size_t words) {
+  if (c->monh.allocated() && c->monh_words >= words) return 0;
+  c->monh.release();
+  c->monh_words = 0;
+  if (c->monh.alloc(words)) return -1;
+  c->monh_words = words;
+  return 0;
+}
+// queues the tables of U into dst[S.words] (device, 64-bit counts); clk != 0: the record that decides, on the device, whether they are
+// taken.  The one place that knows whether the backend has kernels of its own
+int pdfs_queue(rgpu_ctx* c, const double* U, const StepClock* clk, const PdfSet& S, double* dst) {
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(dst);
+#ifdef RGPU_TILED_MONITOR_PDF
+  const unsigned groups = rgpu_tiled::pdf_groups(c->g, rgpu::options().pdf_groups, pdf_scratch_groups(c, S));
+  return rgpu_tiled::launch_monitor_pdf(c->stream, c->g, S, rgpu_tiled::pdf_replicas(S.words, rgpu::options().pdf_replicas), groups, U, clk, reinterpret_cast<unsigned*>(c->F), out);
+#else
+  K_mon_pdf_zero k0 = {S.words, out, clk};
+  K_mon_pdf k1 = {c->g, S, U, out, clk};
+  return (rg_launch<kBlock>(c->stream, S.words, k0) || rg_launch<kBlock>(c->stream, pdf_rows(c->g) * (unsigned)c->g.nx, k1)) ? -1 : 0;
+#endif
+}
+// one sample of U[parity] outside a batch, of a set that was not refused
+int pdfs_take(rgpu_ctx* c, const std::string& who, int parity, const PdfSet& S, void* out) {
+  if (pdf_log_reserve(c, S.words)) return RG_HIPFAIL(c, who + ": device buffer of the counts");
+  if (pdfs_queue(c, c->U[parity & 1], 0, S, c->monh.d) || rg_copy_d2h(out, c->monh.d, S.words * sizeof(unsigned long long), c->stream) || rg_stream_sync(c->stream))
+    return RG_HIPFAIL(c, who);
+  return RGPU_OK;
+}
+int state_pdfs(rgpu_ctx* c, int parity, int npdfs, const rgpu_pdf_spec* specs, unsigned long long* out) {
+  RG_CHECK_CTX(c);
+  const std::string who = "state_pdfs";
+  if (!out || !specs) return fail(c, RGPU_EINVAL, who + ": null pointer");
+  PdfSet S;
+  if (const int rc = pdfs_refusal(c, who, npdfs, specs, &S)) return rc;
+  return pdfs_take(c, who, parity, S, out);
+}
+
+// ---- the samples of a batch: of the monitor, of the plane monitor, of the map monitor or of the PDF monitor -------------------------
+// which sample a call takes (and, for maps and PDFs, of what).  Samples are 8-byte words, doubles or counts: the loop only copies them
+enum MonWhat { MON_MONITOR, MON_PLANES, MON_MAPS, MON_PDFS };
+struct MonSample { MonWhat what; int nmaps; const rgpu_map_spec* specs; const PdfSet* pdf; };
 size_t monitor_sample_doubles(const rgpu_ctx* c, const MonSample& S) {
+  if (S.what == MON_PDFS) return (size_t)S.pdf->words;
   return S.what == MON_MAPS ? maps_sample_doubles(c, S.nmaps, S.specs) : S.what == MON_PLANES ? monp_sample_doubles(c->g) : (size_t)MON_NQ;
 }
-// whether the samples of this context can be taken inside its device-clock batches.  Maps need no scratch: one sample within the budget
+// whether the samples of this context can be taken inside its device-clock batches.  Maps need no scratch: one sample within the
+// budget.  PDFs: their scratch was checked with the specs
 bool monitor_sample_fits(rgpu_ctx* c, const MonSample& S) {
+  if (S.what == MON_PDFS) return true;
   if (S.what == MON_MAPS) return c->g.three_d && monitor_sample_doubles(c, S) <= map_log_budget_doubles();
   return S.what == MON_PLANES ? monitor_planes_scratch_fits(c) : monitor_scratch_fits(c);
 }
-DeviceMirror<double>& monitor_batch_log(rgpu_ctx* c, const MonSample& S) { return S.what == MON_MAPS ? c->monm : S.what == MON_PLANES ? c->monp : c->mon; }
+DeviceMirror<double>& monitor_batch_log(rgpu_ctx* c, const MonSample& S) { return S.what == MON_PDFS ? c->monh : S.what == MON_MAPS ? c->monm : S.what == MON_PLANES ? c->monp : c->mon; }
 // The slots of the log of a call that samples every `every` steps.  The monitor's: a slot per step of a batch.  The plane monitor's:
 // a slot per sample that can fall into one batch.  The maps': as many, or as the budget holds if that is fewer (at least one:
 // monitor_sample_fits)
 size_t monitor_batch_slots(const rgpu_ctx* c, const MonSample& S, int every) {
   if (S.what == MON_MONITOR) return (size_t)rgpu_ctx::kClockBatch;
   const size_t slots = (size_t)rgpu_ctx::kClockBatch / (size_t)every + 1;
-  if (S.what == MON_PLANES) return slots;
+  if (S.what == MON_PLANES || S.what == MON_PDFS) return slots;   // (a PDF sample is at most 128 KiB: no byte budget)
   const size_t held = map_log_budget_doubles() / monitor_sample_doubles(c, S);
   return held < slots ? held : slots;
 }
@@ -183,6 +292,7 @@ int monitor_batch_alloc(rgpu_ctx* c, const MonSample& S, int every) {
   const size_t slots = monitor_batch_slots(c, S, every);
   const size_t n = slots * monitor_sample_doubles(c, S);
   if (S.what == MON_MAPS) return map_log_reserve(c, n);
+  if (S.what == MON_PDFS) return pdf_log_reserve(c, n);
   DeviceMirror<double>& log = monitor_batch_log(c, S);
   if (S.what == MON_PLANES && log.allocated() && c->monp_slots < slots) log.release();
   if (log.allocated()) return 0;
@@ -198,8 +308,9 @@ int monitor_batch_alloc(rgpu_ctx* c, const MonSample& S, int every) {
 int monitor_batch_queue(rgpu_ctx* c, const MonSample& S, int parity, int k) {
   double* dst = monitor_batch_log(c, S).d + (size_t)k * monitor_sample_doubles(c, S);
   const double* U = c->U[parity & 1];
-  const int rc = S.what == MON_MAPS ? maps_queue(c, U, c->clk_cur, S.nmaps, S.specs, dst) : S.what == MON_PLANES ? monitor_planes_queue(c, U, c->clk_cur, dst) : monitor_queue(c, U, c->clk_cur, dst);
-  if (rc == 0) ++(S.what == MON_MAPS ? c->monm_samples : S.what == MON_PLANES ? c->monp_samples : c->mon_samples);
+  const int rc = S.what == MON_PDFS ? pdfs_queue(c, U, c->clk_cur, *S.pdf, dst) : S.what == MON_MAPS ? maps_queue(c, U, c->clk_cur, S.nmaps, S.specs, dst)
+               : S.what == MON_PLANES ? monitor_planes_queue(c, U, c->clk_cur, dst) : monitor_queue(c, U, c->clk_cur, dst);
+  if (rc == 0) ++(S.what == MON_PDFS ? c->monh_samples : S.what == MON_MAPS ? c->monm_samples : S.what == MON_PLANES ? c->monp_samples : c->mon_samples);
   return rc;
 }
 

@@ -22,3 +22,6 @@
 #include "monitor_maps.h"
 // the gfx950 kernels of the map monitor exist (api/monitor.h: without this macro it runs the flat functor)
 #define RGPU_TILED_MONITOR_MAPS 1
+#include "monitor_pdf.h"
+// the gfx950 kernels of the PDF monitor exist (api/monitor.h: without this macro it runs the flat functors)
+#define RGPU_TILED_MONITOR_PDF 1

@@ -871,6 +871,108 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     if (!f) throw std::runtime_error("cannot write " + maps_list);
     f << "# nStep totalTime map axis lo hi file\n";
   }
+  // [pdfs] enabled=yes every=N pdf0=rho:log2:-8:8:3 pdf1=rho:log2:-4:4:2,eint:lin:0:4:32 ... (up to pdf7, numbered from 0 without a
+  // gap): histograms of a 3D single-domain run (include/rgpu.h, "PDF monitors") after every step that brings nStep to a multiple of
+  // `every`.  An axis is channel:lin:lo:hi:nbins or channel:log2:emin:emax:sub (octave bins on |x| from 2^emin to 2^emax, 2^sub
+  // sub-bins each), the channel a name of RGPU_PDF_NAMES; two axes joined by a comma are a joint PDF.  Each sample of each PDF is one
+  // file <outputDir>/<outputPrefix>_pdf<m>_<step, 7 digits>.npy -- NumPy format 1.0, '<u8', C order, shape (na + 3,) or (na + 3, nb + 3)
+  // -- and one line "step t pdf spec file" of <outputPrefix>_pdfs.txt, t with 17 significant digits.  Driven as [maps] is; a batch
+  // serves one consumer, and the PDFs take the batches where the maps do not: otherwise they come from rgpu_state_pdfs at the
+  // sampling steps -- the same words either way.  Not for z-slab, hooked or 2D runs.
+  const bool pdfsEnabled = cfg_.get_bool("pdfs", "enabled", false);
+  const int pdfs_every = pdfsEnabled ? (int)cfg_.get_integer("pdfs", "every", 10) : 0;
+  if (pdfsEnabled && pdfs_every < 1) throw std::runtime_error("[pdfs] every must be at least 1");
+  bool noted_pdfs = false;
+  if (pdfsEnabled && (slab() || hooked_ || p_.nz_global == 1)) note_once(&noted_pdfs, p_.nz_global == 1 ? "2D run: the PDF files are not written" : "z-slab run: the PDF files are not written");
+  std::vector<rgpu_pdf_spec> pdf_specs;
+  std::vector<std::string> pdf_texts;
+  std::vector<size_t> pdf_at(1, 0);   // table m of a sample begins at pdf_at[m]; pdf_at.back(): the words of a sample
+  if (pdfsEnabled && !slab() && !hooked_ && p_.nz_global != 1) {
+    // one axis out of its text; false: the text is not an axis (what the numbers may be is the library's to say)
+    const auto parse_axis = [](const std::string& text, rgpu_pdf_axis* a) {
+      std::vector<std::string> f;
+      for (size_t at = 0;;) {
+        const size_t colon = text.find(':', at);
+        f.push_back(text.substr(at, colon == std::string::npos ? colon : colon - at));
+        if (colon == std::string::npos) break;
+        at = colon + 1;
+      }
+      if (f.size() != 5) return false;
+      std::istringstream names(RGPU_PDF_NAMES);
+      std::string name;
+      a->channel = -1;
+      for (int q = 0; names >> name; ++q) if (name == f[0]) a->channel = q;
+      a->scale = f[1] == "lin" ? 0 : f[1] == "log2" ? 1 : -1;
+      if (a->channel < 0 || a->scale < 0) return false;
+      char* end = 0;
+      double v[3];
+      for (int k = 0; k < 3; ++k) {
+        v[k] = std::strtod(f[2 + k].c_str(), &end);
+        if (f[2 + k].empty() || *end != 0) return false;
+      }
+      if (a->scale == 0) { a->lo = v[0]; a->hi = v[1]; a->nbins = (int)v[2]; a->sub = 0; return v[2] == (double)a->nbins; }
+      if (v[0] != std::floor(v[0]) || v[1] != std::floor(v[1]) || v[2] != std::floor(v[2]) || std::fabs(v[0]) > 1100 || std::fabs(v[1]) > 1100 || v[2] < 0 || v[2] > 6) return false;
+      a->lo = std::ldexp(1.0, (int)v[0]); a->hi = std::ldexp(1.0, (int)v[1]); a->sub = (int)v[2];
+      a->nbins = v[1] > v[0] ? ((int)v[1] - (int)v[0]) << a->sub : 0;
+      return true;
+    };
+    size_t total = 0;
+    for (int m = 0; m < RGPU_PDF_MAX; ++m) {
+      const std::string key = "pdf" + std::to_string(m), text = cfg_.get_string("pdfs", key, "");
+      if (text.empty()) break;
+      rgpu_pdf_spec sp = {};
+      const size_t comma = text.find(',');
+      const bool ok = parse_axis(text.substr(0, comma), &sp.a) && (comma == std::string::npos || (parse_axis(text.substr(comma + 1), &sp.b) && sp.b.nbins != 0));
+      const size_t words = ok ? rgpu_pdf_words(&sp) : 0;
+      if (words == 0)
+        throw std::runtime_error("[pdfs] " + key + "=" + text + ": expected channel:lin:lo:hi:nbins or channel:log2:emin:emax:sub (a channel of \"" RGPU_PDF_NAMES "\"; lo < hi; sub 0 .. 6), or two of them joined by a comma, within " + std::to_string(RGPU_PDF_MAX_WORDS) + " words");
+      total += words;
+      if (total > (size_t)RGPU_PDF_MAX_WORDS) throw std::runtime_error("[pdfs] " + key + ": the PDFs have more than " + std::to_string(RGPU_PDF_MAX_WORDS) + " words together");
+      pdf_specs.push_back(sp);
+      pdf_texts.push_back(text);
+      pdf_at.push_back(total);
+    }
+  }
+  const bool pdfs_on = !pdf_specs.empty();
+  const std::string pdfs_list = rs_.outputDir + "/" + rs_.outputPrefix + "_pdfs.txt";
+  // n samples of all PDFs: the .npy files and their lines in the list
+  const auto pdfs_files = [&](int n, const int* step, const double* t, const unsigned long long* v) {
+    std::ofstream list(pdfs_list.c_str(), std::ios::app);
+    if (!list) throw std::runtime_error("cannot write " + pdfs_list);
+    char num[64];
+    for (int k = 0; k < n; ++k)
+      for (size_t m = 0; m < pdf_specs.size(); ++m) {
+        const rgpu_pdf_spec& sp = pdf_specs[m];
+        std::snprintf(num, sizeof(num), "_pdf%d_%07d.npy", (int)m, step[k]);
+        const std::string name = rs_.outputPrefix + num, path = rs_.outputDir + "/" + name;
+        // NumPy format 1.0, as the maps' files: the header padded with spaces to a multiple of 64
+        const std::string shape = sp.b.nbins == 0 ? std::to_string(sp.a.nbins + 3) + "," : std::to_string(sp.a.nbins + 3) + ", " + std::to_string(sp.b.nbins + 3);
+        std::string head = "{'descr': '<u8', 'fortran_order': False, 'shape': (" + shape + "), }";
+        head.append(63 - (10 + head.size()) % 64, ' ');
+        head += "\n";
+        std::ofstream f(path.c_str(), std::ios::binary | std::ios::trunc);
+        const char magic[10] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0, (char)(head.size() & 0xff), (char)(head.size() >> 8)};
+        f.write(magic, 10);
+        f.write(head.data(), (std::streamsize)head.size());
+        f.write(reinterpret_cast<const char*>(v + (size_t)k * pdf_at.back() + pdf_at[m]), (std::streamsize)((pdf_at[m + 1] - pdf_at[m]) * sizeof(unsigned long long)));
+        if (!f) throw std::runtime_error("cannot write " + path);
+        std::snprintf(num, sizeof(num), " %.17g", t[k]);
+        list << step[k] << num << " " << m << " " << pdf_texts[m] << " " << name << "\n";
+      }
+  };
+  std::vector<unsigned long long> pdfs_v;
+  std::vector<int> pdfs_step;
+  std::vector<double> pdfs_t;
+  const auto pdfs_direct = [&](int n) {   // the PDFs of the current state U[n % 2]
+    pdfs_v.resize(std::max(pdfs_v.size(), pdf_at.back()));
+    check(rgpu_state_pdfs(ctx_, n % 2, (int)pdf_specs.size(), pdf_specs.data(), pdfs_v.data()), "state_pdfs");
+    pdfs_files(1, &n, &totalTime_, pdfs_v.data());
+  };
+  if (pdfs_on && !(totalTime_ > 0)) {   // the start of a run
+    std::ofstream f(pdfs_list.c_str(), std::ios::trunc);
+    if (!f) throw std::runtime_error("cannot write " + pdfs_list);
+    f << "# nStep totalTime pdf spec file\n";
+  }
   const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   while (totalTime_ < rs_.tEnd && nStep < rs_.nStepmax) {
     if (rs_.nLog > 0 && (nStep % rs_.nLog) == 0 && p_.slab_rank == 0)
@@ -903,11 +1005,21 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     }
     // a batch serves one consumer: where the maps take it, the monitor rows come from the direct calls
     const bool maps_batched = maps_on && !historyEnabled && quiet > 1;
-    const bool monitor_batched = monitor_on && !historyEnabled && quiet > 1 && !maps_batched;
+    const bool pdfs_batched = pdfs_on && !historyEnabled && quiet > 1 && !maps_batched;
+    const bool monitor_batched = monitor_on && !historyEnabled && quiet > 1 && !maps_batched && !pdfs_batched;
     if (monitor_on && !monitor_batched && mon_every - nStep % mon_every < quiet) quiet = mon_every - nStep % mon_every;   // the direct call follows
     if (maps_on && !maps_batched && maps_every - nStep % maps_every < quiet) quiet = maps_every - nStep % maps_every;      // the direct call follows
+    if (pdfs_on && !pdfs_batched && pdfs_every - nStep % pdfs_every < quiet) quiet = pdfs_every - nStep % pdfs_every;      // the direct call follows
     const int nStep_before = nStep;
-    if (maps_batched) {
+    if (pdfs_batched) {
+      int mn = 0;
+      const size_t cap = (size_t)(quiet / pdfs_every + 1);
+      if (pdfs_step.size() < cap) { pdfs_step.resize(cap); pdfs_t.resize(cap); }
+      if (pdfs_v.size() < cap * pdf_at.back()) pdfs_v.resize(cap * pdf_at.back());
+      const int rc = rgpu_run_steps_pdfs(ctx_, quiet, rs_.tEnd, &nStep, &totalTime_, &dt, 0, pdfs_every, (int)pdf_specs.size(), pdf_specs.data(), &mn, pdfs_step.data(), pdfs_t.data(), pdfs_v.data());
+      pdfs_files(mn, pdfs_step.data(), pdfs_t.data(), pdfs_v.data());
+      if (rc < 0) check(rc, "run_steps_pdfs");
+    } else if (maps_batched) {
       int mn = 0;
       const size_t cap = (size_t)(quiet / maps_every + 1);
       if (maps_step.size() < cap) { maps_step.resize(cap); maps_t.resize(cap); }
@@ -949,6 +1061,7 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     }
     if (monitor_on && !monitor_batched && nStep > nStep_before && nStep % mon_every == 0) monitor_direct(nStep);
     if (maps_on && !maps_batched && nStep > nStep_before && nStep % maps_every == 0) maps_direct(nStep);
+    if (pdfs_on && !pdfs_batched && nStep > nStep_before && nStep % pdfs_every == 0) pdfs_direct(nStep);
   }
   check(rgpu_synchronize(ctx_), "synchronize");
   if (hooked_) hook_check(hooks_.barrier(hooks_.self), "barrier");

@@ -18,6 +18,8 @@ struct Options {
   int member_params = 0;  // 1: the fused rounds of every ensemble read their constants from the per-member table (hip/ensemble_scan.h), equal sets or not
   int map_log_kib = 262144;   // byte budget (KiB) of the device log of the maps a batch samples (api/monitor.h; rgpu_run_steps_mapped)
   int map_x_tiled = -1;   // the kernel that sums a map along x (hip/monitor_maps.h): -1 by the thickness of the range, 0 direct, 1 tiled
+  int pdf_replicas = -1;  // copies of the LDS table of the PDF monitor's count kernel (hip/monitor_pdf.h): -1 automatic, n forces the count (the same words)
+  int pdf_groups = -1;    // workgroups of that kernel: -1 automatic, n forces the grid size (the same words)
 };
 inline Options& options() { static Options o; return o; }
 inline int* option_slot(const char* name) {
@@ -33,6 +35,8 @@ inline int* option_slot(const char* name) {
   if (!std::strcmp(name, "member_params")) return &o.member_params;
   if (!std::strcmp(name, "map_log_kib")) return &o.map_log_kib;
   if (!std::strcmp(name, "map_x_tiled")) return &o.map_x_tiled;
+  if (!std::strcmp(name, "pdf_replicas")) return &o.pdf_replicas;
+  if (!std::strcmp(name, "pdf_groups")) return &o.pdf_groups;
   return 0;
 }
 

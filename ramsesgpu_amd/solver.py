@@ -21,6 +21,32 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 MonitorSeries = collections.namedtuple("MonitorSeries", "step t values")
 # the series out of run_steps_mapped: step numbers [n], times [n], and per spec an array [n, 12, nv, nu] (channels _capi.MAP_NAMES)
 MapSeries = collections.namedtuple("MapSeries", "step t maps")
+# the series out of run_steps_pdfs: step numbers [n], times [n], and per spec an array of uint64 [n, na + 3] or [n, na + 3, nb + 3]
+PdfSeries = collections.namedtuple("PdfSeries", "step t pdfs")
+
+
+def pdf_axis(axis):
+    """an axis of a PDF as _capi.RgpuPdfAxis, from one, or from (channel, "lin", lo, hi, nbins) / (channel, "log2", emin, emax, sub) --
+    the channel a name of _capi.PDF_NAMES or its index; "log2": octave bins on |x| from 2^emin to 2^emax, 2^sub sub-bins each"""
+    if isinstance(axis, _capi.RgpuPdfAxis):
+        return axis
+    ch, scale, a, b, n = axis
+    ch = _capi.PDF_NAMES.index(ch) if isinstance(ch, str) else int(ch)
+    if scale == "lin":
+        return _capi.RgpuPdfAxis(ch, 0, int(n), 0, float(a), float(b))
+    if scale != "log2":
+        raise ValueError('the scale of a PDF axis is "lin" or "log2"')
+    return _capi.RgpuPdfAxis(ch, 1, max(int(b) - int(a), 0) << int(n), int(n), float(np.ldexp(1.0, int(a))), float(np.ldexp(1.0, int(b))))
+
+
+def pdf_edges(axis):
+    """the nbins + 1 edges of the bins of an axis: exact for octave bins (every edge is a double), the nominal lo + b (hi - lo) / nbins
+    for linear ones (the library classifies by (x - lo) * (nbins / (hi - lo)), include/rgpu.h)"""
+    a = pdf_axis(axis)
+    b = np.arange(a.nbins + 1)
+    if a.scale == 0:
+        return a.lo + b * (a.hi - a.lo) / a.nbins
+    return np.ldexp(a.lo * (1.0 + (b % (1 << a.sub)) / float(1 << a.sub)), b >> a.sub)
 
 
 def lib_path(arithmetic=None):
@@ -356,6 +382,51 @@ class Solver:
             self._chk(done, "run_steps_mapped")
         self.dt_log = [log[i] for i in range(done)]
         return done, self.map_series
+
+    def _pdf_specs(self, specs):
+        """specs, each an axis (1D) or a pair of axes (joint), an axis as pdf_axis takes it -> (the C array, the shape of each table)"""
+        arr = (_capi.RgpuPdfSpec * max(len(specs), 1))()
+        shapes = []
+        for m, spec in enumerate(specs):
+            joint = isinstance(spec, (tuple, list)) and len(spec) == 2 and isinstance(spec[0], (tuple, list, _capi.RgpuPdfAxis))
+            arr[m].a = pdf_axis(spec[0] if joint else spec)
+            if joint:
+                arr[m].b = pdf_axis(spec[1])
+            shapes.append((arr[m].a.nbins + 3, arr[m].b.nbins + 3) if joint else (arr[m].a.nbins + 3,))
+        return arr, shapes
+
+    def state_pdfs(self, specs, parity=None):
+        """histograms of the interior cells of U[parity] (default: nStep % 2) of a 3D state: a list, per spec, of numpy.uint64 counts
+        shaped (na + 3,) -- the bins, then under, over, nan -- or (na + 3, nb + 3) for a pair of axes (rgpu_state_pdfs; include/rgpu.h,
+        "PDF monitors")"""
+        arr, shapes = self._pdf_specs(specs)
+        out = np.zeros(max(sum(int(np.prod(s)) for s in shapes), 1), dtype=np.uint64)
+        par = self.nStep % 2 if parity is None else int(parity)
+        self._chk(self.lib.rgpu_state_pdfs(self.ctx, par, len(specs), arr, out.ctypes.data_as(C.POINTER(C.c_ulonglong))), "state_pdfs")
+        cuts = np.cumsum([0] + [int(np.prod(s)) for s in shapes])
+        return [out[cuts[m]:cuts[m + 1]].reshape(shapes[m]).copy() for m in range(len(specs))]
+
+    def run_steps_pdfs(self, nsteps, every, specs, tEnd=float("inf")):
+        """run_steps with a sample of the PDFs `specs` after every step that brings nStep to a multiple of `every` (rgpu_run_steps_pdfs:
+        inside the device-clock batches the cells are counted on the device, one read-back per batch).  Returns (done, PdfSeries): the
+        steps done and the samples of this call -- .step [n], .t [n] (the time after that step), .pdfs a list per spec of numpy.uint64
+        [n, na + 3] or [n, na + 3, nb + 3]"""
+        arr, shapes = self._pdf_specs(specs)
+        sizes = [int(np.prod(s)) for s in shapes]
+        cap = max(int(nsteps), 0) // max(int(every), 1) + 1
+        n, t, d, mn = C.c_int(self.nStep), C.c_double(self.totalTime), C.c_double(self.dt), C.c_int(0)
+        log = (C.c_double * max(int(nsteps), 1))()
+        mstep, mt, mv = np.zeros(cap, dtype=np.intc), np.zeros(cap), np.zeros((cap, max(sum(sizes), 1)), dtype=np.uint64)
+        done = self.lib.rgpu_run_steps_pdfs(self.ctx, int(nsteps), float(tEnd), C.byref(n), C.byref(t), C.byref(d), log, int(every), len(specs), arr, C.byref(mn),
+                                            mstep.ctypes.data_as(C.POINTER(C.c_int)), mt.ctypes.data_as(_capi.c_double_p), mv.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+        k = mn.value
+        self.nStep, self.totalTime, self.dt = n.value, t.value, d.value   # (they describe the steps that ran, also when the call failed)
+        cuts = np.cumsum([0] + sizes)
+        self.pdf_series = PdfSeries(mstep[:k].astype(int), mt[:k].copy(), [mv[:k, cuts[m]:cuts[m + 1]].reshape((k,) + shapes[m]).copy() for m in range(len(specs))])
+        if done < 0:
+            self._chk(done, "run_steps_pdfs")
+        self.dt_log = [log[i] for i in range(done)]
+        return done, self.pdf_series
 
     def history_turbulence(self, nStep=None):
         """history_turbulence (MHDRunBase.cpp:3626-3810) reduced on the device: the 18 columns after totalTime and dt"""
