@@ -797,6 +797,84 @@ int rgpu_run_steps_pdfs(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double
                         unsigned long long* pdfs /* [cap][sum of rgpu_pdf_words] */);
 long rgpu_pdf_batch_samples(rgpu_ctx* c);
 
+/* ---- spectrum monitors: shell-binned power spectra of a 3D state, taken on the device -------------------------------------------------
+ * The power per wave-number shell is the fifth shape of the family: E(k) of a turbulent box, the kinetic, magnetic and density spectra
+ * of an MRI run, the one-dimensional spectra along an axis.  The box is a single-domain 3D context whose nx, ny, nz are each a power
+ * of two from 4 to 1024, and it is treated as PERIODIC in all three directions whatever its boundary conditions are: only the
+ * N = nx ny nz interior cells of U[parity] are read, as the array stands, hydro or MHD.  No ghost fill is done; the cell-centred B of
+ * the last interior row, column and plane takes its high faces from the first ghost layer, as for the plane monitor.  In a shearing
+ * box the transform is the plain lab-frame one: no remap to shearing coordinates is done, so between the periodic points of the shear
+ * the x direction is not periodic and the spectra along x carry the jump.
+ * Channels, in the order of RGPU_SPECTRUM_NAMES: rho, mx my mz and bx by bz are columns 0, 1 2 3 and 10 11 12 of the plane monitor's
+ * per-cell terms above (csrc/kernels_monitor_spectrum.h picks them, it restates nothing); v = m / rho; w = m / sqrt(rho), the
+ * density-weighted velocity, whose spectrum sums to twice the kinetic energy per cell.  v and w are formed from those terms with the
+ * library's division and square root (exactly rounded in librgpu.so, within a few ulp in librgpu_fast.so), not contracted.  For a hydro
+ * state bx, by, bz are exactly +0.0.
+ * A spec: { channels; wx, wy, wz }.  `channels` is a non-empty bit mask over the RGPU_SPECTRUM_NQ channels (bit q: channel q); the
+ * weights are integers 0 .. RGPU_SPECTRUM_MAX_WEIGHT, not all zero.  With u_c a channel,
+ *   u^_c(k) = (1 / N) sum_x u_c(x) exp(-2 pi i (kx i / nx + ky j / ny + kz k / nz)),
+ * k the integer wave vector, k_a folded to -n_a / 2 .. n_a / 2 - 1.  The shell of a mode is defined in integers: with
+ * q = (wx kx)^2 + (wy ky)^2 + (wz kz)^2, shell s is the s >= 0 with s^2 - s + 1 <= q <= s^2 + s (shell 0: q = 0).  That is
+ * round(sqrt(q)) with every edge exact; no square root is evaluated.  A spec has S = shell(sum_a (w_a n_a / 2)^2) + 1 shells, at most
+ * RGPU_SPECTRUM_MAX_SHELLS.  Its output is 2 S doubles:
+ *   P[s] = sum over the modes k of shell s, over the channels c of the mask, of |u^_c(k)|^2
+ *   M[s] = the number of modes of shell s, as a double (an exact integer).
+ * Weights (1, 1, 1): the isotropic spectrum in units of the fundamental; (4, 1, 4): physical shells of a 1 : 4 : 1 box in units of
+ * 2 pi / Ly; (0, 1, 0): the one-dimensional spectrum along y, summed over kx and kz, the shell |ky|.  Identities: sum_s P[s] =
+ * (1 / N) sum_x sum_c u_c^2 (Parseval) to rounding; sum_s M[s] = N exactly.
+ * How it is computed (csrc/hip/monitor_spectrum.h): per pair of channels a, b of the mask in ascending order (an odd
+ * last one with zero) ONE complex transform of Z = a + i b -- every shell is symmetric under k -> -k, so the shell sums of |Z^|^2 are
+ * those of |a^|^2 + |b^|^2 -- in three passes of radix-2 line transforms, x, y, z, each with the whole line in LDS, twiddle factors
+ * from one table computed on the host; the z pass bins |Z^|^2 without writing Z^ back.  All work lies in the flux array, which is
+ * dead between two steps.
+ * Reproducibility: within one library the same state and spec give the same doubles bit for bit, on every call, wherever in a batch
+ * the sample is taken, whatever other specs share the call, and for every value of option "spectrum_tile_y".  No floating-point
+ * atomics: in a workgroup a shell has one owner per part of a tile's columns (parts and tiles assigned by the box and the spec alone),
+ * who adds tile after tile, column after column, |kz| ascending, +kz before -kz; the partial sums are added in the order workgroup,
+ * part, in sixteen runs whose sums are added ascending, and the result is stored.  M is the same in both libraries, word for
+ * word.  P differs between librgpu.so, librgpu_fast.so and another FFT by rounding: the transforms are backward stable, |dP[s]| <=
+ * e (P[s] + 2 sqrt(P[s] Ptot)) + e^2 Ptot with e the relative L2 error of the transforms (tests: e = 1e-12; measured: DESIGN 3.4.6).
+ *
+ *   rgpu_spectrum_shells        S of *spec on this context; 0 for a context or a spec that is refused.
+ *   rgpu_state_spectra          nspec outputs of U[parity], one after another in `out` (spec m at the sum of 2 S of the specs before
+ *                               it: P[0 .. S), then M[0 .. S)).  Reads the state only: ghost cells, CFL slots and what the context knows
+ *                               about them stay as they are.  Synchronises.
+ *   rgpu_run_steps_spectra      rgpu_run_steps_log (same states, same dt sequence, same return value) plus sampling, with the semantics
+ *                               of rgpu_run_steps_pdfs word for word: a sample (all nspec outputs) after each step that brings *nStep to
+ *                               a multiple of `every`; *mon_n = the samples of this call (<= cap = nsteps / every + 1); sample k:
+ *                               mon_step[k], mon_t[k] the host-accumulated *t after that step, spectra + k * W (W = the sum of 2 S over
+ *                               the specs) what rgpu_state_spectra gives on that state, bit for bit.  A step that reaches tEnd is
+ *                               sampled if it qualifies, nothing is sampled after a stop; *mon_n counts only samples whose values were
+ *                               written.  A run cut into calls gives the series of one call.  dt_log may be NULL.  Where the context
+ *                               takes its time step from the device (rgpu_device_time_step_ready) the kernels of a sample are queued
+ *                               behind the last kernel of each qualifying step, return in their first instructions when the step's clock
+ *                               record says stop, and store to a device log that is copied back once per batch with the clock records.
+ *                               Everywhere else the call is the literal loop: rgpu_one_step_integration, then rgpu_state_spectra.  The
+ *                               log has RGPU_CLOCK_BATCH / every + 1 slots, is allocated by the first call that needs it, grown between
+ *                               batches if a later call needs more, freed with the context, and is not part of rgpu_device_bytes; nor
+ *                               is the table of twiddle factors (8 KiB, uploaded by the first call that needs it, freed with the context).
+ *   rgpu_spectrum_batch_samples how many samples this context has queued on the device inside its batches so far (0 where every call
+ *                               took the literal loop).  These calls leave the other monitors' counters alone.
+ *   Errors (nothing has run, *mon_n == 0): RGPU_EUNSUPPORTED for a 2D context ("3D" in the message) and for an extent that is not a
+ *                               power of two in 4 .. 1024 (the message names it, "nx = 65 ..."); RGPU_EINVAL for a slab context
+ *                               (slab_count > 1), a NULL pointer among nStep, t, dt, specs, mon_n, mon_step, mon_t, spectra / out,
+ *                               nsteps < 0, every < 1 ("every" in the message), nspec outside 1 .. RGPU_SPECTRUM_MAX, an empty mask or
+ *                               one with bits beyond the channels, a weight outside 0 .. RGPU_SPECTRUM_MAX_WEIGHT, all weights zero,
+ *                               more than RGPU_SPECTRUM_MAX_SHELLS shells (the message names the spec, "spectrum 1: ..."), or a flux
+ *                               array too small for the transform and the partial sums. */
+#define RGPU_SPECTRUM_NQ 13
+#define RGPU_SPECTRUM_NAMES "rho mx my mz vx vy vz wx wy wz bx by bz"   /* the RGPU_SPECTRUM_NQ channels, in order */
+#define RGPU_SPECTRUM_MAX 4                                            /* specs per call */
+#define RGPU_SPECTRUM_MAX_SHELLS 4096                                  /* shells of one spec */
+#define RGPU_SPECTRUM_MAX_WEIGHT 64                                    /* largest weight of an axis */
+typedef struct { unsigned channels; int wx, wy, wz; } rgpu_spectrum_spec;
+int rgpu_spectrum_shells(rgpu_ctx* c, const rgpu_spectrum_spec* spec);
+int rgpu_state_spectra(rgpu_ctx* c, int parity, int nspec, const rgpu_spectrum_spec* specs, double* out);
+int rgpu_run_steps_spectra(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log,
+                           int every, int nspec, const rgpu_spectrum_spec* specs, int* mon_n, int* mon_step /* [cap] */, double* mon_t /* [cap] */,
+                           double* spectra /* [cap][sum of 2 S] */);
+long rgpu_spectrum_batch_samples(rgpu_ctx* c);
+
 /* Self-test of the device arithmetic the parity contract rests on: for n operand pairs computes on the device
  *   quot[i]  = rg_div(num[i], rg_recip(den[i]))   the shared-reciprocal division of csrc/hip/rg_backend.h
  *   quot2[i] = num[i] / den[i]                    the compiler's IEEE division
@@ -843,8 +921,9 @@ int rgpu_selftest_alfven(const rgpu_params* p, int n, const double* states36, do
  *   "map_x_tiled" (-1)  which kernel sums a map along x: -1 by the thickness of the range, 0 the direct one, 1 the tiled one (the same bits)
  *   "pdf_replicas" (-1) copies of the LDS table of counts the PDF monitor's kernel keeps: -1 automatic, n forces the count (the same words)
  *   "pdf_groups" (-1)   workgroups of that kernel: -1 automatic, n forces the grid size (the same words)
+ *   "spectrum_tile_y" (-1) log2 of the adjacent x a tile of the spectrum monitor's y pass holds: -1 the widest that fits, 0 .. 6 forces it (the same doubles)
  * rgpu_set_option returns the previous value (-1: unknown name; the options above are never negative except "as created" and the
- * defaults of "map_x_tiled", "pdf_replicas" and "pdf_groups"). */
+ * defaults of "map_x_tiled", "pdf_replicas", "pdf_groups" and "spectrum_tile_y"). */
 int rgpu_set_option(const char* name, int value);
 int rgpu_get_option(const char* name);
 

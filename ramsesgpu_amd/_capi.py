@@ -22,6 +22,12 @@ PDF_NAMES = ("rho", "mx", "my", "mz", "E", "ekin", "emag", "eint", "bx", "by", "
 PDF_NQ = len(PDF_NAMES)
 PDF_MAX = 8
 PDF_MAX_WORDS = 16384
+# the channels of a spectrum (rgpu_state_spectra, rgpu_run_steps_spectra): RGPU_SPECTRUM_NQ = 13, bit q of a spec's mask is channel q
+SPECTRUM_NAMES = ("rho", "mx", "my", "mz", "vx", "vy", "vz", "wx", "wy", "wz", "bx", "by", "bz")
+SPECTRUM_NQ = len(SPECTRUM_NAMES)
+SPECTRUM_MAX = 4
+SPECTRUM_MAX_SHELLS = 4096
+SPECTRUM_MAX_WEIGHT = 64
 T_NAMES = ["boundaries", "prim", "elec", "trace", "flux", "emf", "update", "shear", "dt", "dissipative", "sweep"]
 
 
@@ -93,6 +99,11 @@ class RgpuPdfAxis(C.Structure):
 class RgpuPdfSpec(C.Structure):
     """rgpu_pdf_spec: b.nbins == 0: the 1D histogram of a; else the joint table [a.nbins + 3][b.nbins + 3]"""
     _fields_ = [("a", RgpuPdfAxis), ("b", RgpuPdfAxis)]
+
+
+class RgpuSpectrumSpec(C.Structure):
+    """rgpu_spectrum_spec: the bit mask of the channels and the integer weights of the shell rule"""
+    _fields_ = [("channels", C.c_uint), ("wx", C.c_int), ("wy", C.c_int), ("wz", C.c_int)]
 
 
 def declare_host_api(lib):
@@ -275,6 +286,16 @@ def declare_device_api(lib):
                                             C.c_int, C.POINTER(RgpuPdfSpec), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_u64_p]
         lib.rgpu_pdf_batch_samples.restype = C.c_long
         lib.rgpu_pdf_batch_samples.argtypes = [ctx]
+    if hasattr(lib, "rgpu_state_spectra"):   # (absent from an older build of the library)
+        lib.rgpu_spectrum_shells.restype = C.c_int
+        lib.rgpu_spectrum_shells.argtypes = [ctx, C.POINTER(RgpuSpectrumSpec)]
+        lib.rgpu_state_spectra.restype = C.c_int
+        lib.rgpu_state_spectra.argtypes = [ctx, C.c_int, C.c_int, C.POINTER(RgpuSpectrumSpec), c_double_p]
+        lib.rgpu_run_steps_spectra.restype = C.c_int
+        lib.rgpu_run_steps_spectra.argtypes = [ctx, C.c_int, C.c_double, C.POINTER(C.c_int), c_double_p, c_double_p, c_double_p, C.c_int,
+                                               C.c_int, C.POINTER(RgpuSpectrumSpec), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]
+        lib.rgpu_spectrum_batch_samples.restype = C.c_long
+        lib.rgpu_spectrum_batch_samples.argtypes = [ctx]
     return lib
 
 
@@ -328,4 +349,5 @@ DECLARED_SYMBOLS = [
     "rgpu_state_monitor_planes", "rgpu_run_steps_monitored_planes", "rgpu_monitor_planes_batch_samples",
     "rgpu_map_doubles", "rgpu_state_maps", "rgpu_run_steps_mapped", "rgpu_map_batch_samples",
     "rgpu_pdf_words", "rgpu_state_pdfs", "rgpu_run_steps_pdfs", "rgpu_pdf_batch_samples",
+    "rgpu_spectrum_shells", "rgpu_state_spectra", "rgpu_run_steps_spectra", "rgpu_spectrum_batch_samples",
 ]

@@ -115,6 +115,12 @@ struct rgpu_ctx {
   DeviceMirror<double> monh;
   size_t monh_words = 0;
   long monh_samples = 0;        // PDF samples queued on the device inside batches so far (rgpu_pdf_batch_samples)
+  // the spectra (kernels_monitor_spectrum.h; rgpu_state_spectra, rgpu_run_steps_spectra): the device buffer the last kernel of a sample
+  // stores to -- one sample taken outside a batch at its head, or the samples of a batch; mons_doubles doubles, grown by a call that
+  // needs more.  montw: the table of twiddle factors (spec_twiddle_table), computed and uploaded by the first call that needs it
+  DeviceMirror<double> mons, montw;
+  size_t mons_doubles = 0;
+  long mons_samples = 0;        // spectrum samples queued on the device inside batches so far (rgpu_spectrum_batch_samples)
   // fused 2D steps: the clock is folded into the step kernel itself (step_clock_rec.h: ClockFold) over three rotating slot arrays;
   // d_red always points at the array that holds the maxima of the current state
   unsigned long long* d_red_base = 0;   // 3 x RG_DT_SLOTS

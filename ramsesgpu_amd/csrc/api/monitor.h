@@ -1,8 +1,8 @@
 // api/monitor.h -- the monitor of a lone context on the host side (kernels_monitor.h): scratch extent and launches of one sample, for
 // rgpu_state_monitor (2D), rgpu_state_monitor3d and a sample queued inside a device-clock batch (rgpu_run_steps_monitored); the same for
 // the plane monitor (kernels_monitor_planes.h: rgpu_state_monitor_planes, rgpu_run_steps_monitored_planes) and for the map monitor
-// (kernels_monitor_maps.h: rgpu_state_maps, rgpu_run_steps_mapped) and for the PDF monitor (kernels_monitor_pdf.h: rgpu_state_pdfs,
-// rgpu_run_steps_pdfs).  See api/ctx.h.
+// (kernels_monitor_maps.h: rgpu_state_maps, rgpu_run_steps_mapped), for the PDF monitor (kernels_monitor_pdf.h: rgpu_state_pdfs,
+// rgpu_run_steps_pdfs) and for the spectrum monitor (kernels_monitor_spectrum.h: rgpu_state_spectra, rgpu_run_steps_spectra).  See api/ctx.h.
 #pragma once
 namespace {
 // One route for either dimension, a 2D state being a volume of one plane.  Everything on the device, the sum over the planes included,
@@ -255,29 +255,142 @@ int state_pdfs(rgpu_ctx* c, int parity, int npdfs, const rgpu_pdf_spec* specs, u
   return pdfs_take(c, who, parity, S, out);
 }
 
-// ---- the samples of a batch: of the monitor, of the plane monitor, of the map monitor or of the PDF monitor -------------------------
+// ---- the spectrum monitor (kernels_monitor_spectrum.h): the same consumer with a fifth sample, 2 S doubles per spec -------------------
+static_assert(SPEC_NQ == RGPU_SPECTRUM_NQ && SPEC_MAX == RGPU_SPECTRUM_MAX && SPEC_MAX_SHELLS == RGPU_SPECTRUM_MAX_SHELLS && SPEC_MAX_WEIGHT == RGPU_SPECTRUM_MAX_WEIGHT,
+              "include/rgpu.h states the channels and the limits of the spectra");
+// "" for a box the transforms can take, else what is wrong with it
+std::string spectrum_box_error(const rgpu_ctx* c) {
+  const int n[3] = {c->g.nx, c->g.ny, c->g.nz};
+  for (int a = 0; a < 3; ++a)
+    if (spec_log2(n[a]) < 0) return std::string("n") + "xyz"[a] + " = " + std::to_string(n[a]) + " is not a power of two in 4 .. 1024";
+  return "";
+}
+// "" for a spec this context can take, else what is wrong with it (the box can be taken)
+std::string spectrum_spec_error(const rgpu_ctx* c, const rgpu_spectrum_spec& s) {
+  if (s.channels == 0) return "the channel mask is empty";
+  if (s.channels >> RGPU_SPECTRUM_NQ) return "the channel mask has bits beyond the " + std::to_string(RGPU_SPECTRUM_NQ) + " channels";
+  const int w[3] = {s.wx, s.wy, s.wz};
+  for (int a = 0; a < 3; ++a)
+    if (w[a] < 0 || w[a] > RGPU_SPECTRUM_MAX_WEIGHT) return std::string("w") + "xyz"[a] + " must be 0 .. " + std::to_string(RGPU_SPECTRUM_MAX_WEIGHT);
+  if (s.wx == 0 && s.wy == 0 && s.wz == 0) return "the weights are all zero";
+  const unsigned long long shells = spec_shell_count(spec_box(c->g), s.wx, s.wy, s.wz);
+  if (shells > (unsigned long long)RGPU_SPECTRUM_MAX_SHELLS) return std::to_string(shells) + " shells, more than " + std::to_string(RGPU_SPECTRUM_MAX_SHELLS);
+  return "";
+}
+// the shells of a spec on this context, 0 if the context or the spec is refused
+int spectrum_shells(const rgpu_ctx* c, const rgpu_spectrum_spec* s) {
+  if (!c || !s || !c->U[0] || !c->g.three_d || c->p.slab_count > 1 || !spectrum_box_error(c).empty() || !spectrum_spec_error(c, *s).empty()) return 0;
+  return (int)spec_shell_count(spec_box(c->g), s->wx, s->wy, s->wz);
+}
+// the device buffer the samples are stored to, at least `doubles` long: grown between two batches or two calls, when nothing is in
+// flight.  Not zeroed: every double that is read was stored by the last kernel of a sample.  != 0: it is not there
+int spectrum_log_reserve(rgpu_ctx* c, size_t doubles) {
+  if (c->mons.allocated() && c->mons_doubles >= doubles) return 0;
+  c->mons.release();
+  c->mons_doubles = 0;
+  if (c->mons.alloc(doubles)) return -1;
+  c->mons_doubles = doubles;
+  return 0;
+}
+// the twiddle factors on the device: computed and uploaded by the first call that needs them, kept with the context
+int spectrum_twiddles(rgpu_ctx* c) {
+  if (c->montw.allocated()) return 0;
+  if (c->montw.alloc(2 * (size_t)SPEC_TW)) return -1;
+  spec_twiddle_table(c->montw.h);
+  if (c->montw.upload(2 * (size_t)SPEC_TW, c->stream) == 0) return 0;
+  c->montw.release();
+  return -1;
+}
+// what rgpu_state_spectra and rgpu_run_steps_spectra refuse alike, in this order; 0: the spectra can be taken, and *S is what the kernels read
+int spectra_refusal(rgpu_ctx* c, const std::string& who, int nspec, const rgpu_spectrum_spec* specs, SpecSet* S) {
+  if (!c->U[0]) return fail(c, RGPU_EINVAL, who + ": context without state");
+  if (!c->g.three_d) return fail(c, RGPU_EUNSUPPORTED, who + ": 3D contexts only");
+  const std::string box = spectrum_box_error(c);
+  if (!box.empty()) return fail(c, RGPU_EUNSUPPORTED, who + ": " + box);
+  if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, who + ": single-domain contexts only (a slab holds a part of the box)");
+  if (nspec < 1 || nspec > RGPU_SPECTRUM_MAX) return fail(c, RGPU_EINVAL, who + ": nspec must be 1 .. " + std::to_string(RGPU_SPECTRUM_MAX));
+  const SpecBox b = spec_box(c->g);
+  unsigned doubles = 0, most = 0;
+  for (int m = 0; m < nspec; ++m) {
+    const std::string why = spectrum_spec_error(c, specs[m]);
+    if (!why.empty()) return fail(c, RGPU_EINVAL, who + ": spectrum " + std::to_string(m) + ": " + why);
+    SpecOne& o = S->s[m];
+    o.channels = specs[m].channels; o.wx = specs[m].wx; o.wy = specs[m].wy; o.wz = specs[m].wz;
+    o.shells = (int)spec_shell_count(b, o.wx, o.wy, o.wz);
+    o.base = doubles;
+    doubles += 2u * (unsigned)o.shells;
+    if ((unsigned)o.shells > most) most = (unsigned)o.shells;
+  }
+  S->n = nspec;
+  S->doubles = doubles;
+  if (!c->F || spec_scratch_doubles(b, most) > (size_t)c->g.fN * plan_for(c->p).f) return fail(c, RGPU_EINVAL, who + ": no scratch for the transform and the partial sums");
+  if (spectrum_twiddles(c)) return RG_HIPFAIL(c, who + ": table of the twiddle factors");
+  return RGPU_OK;
+}
+// queues the spectra of U into dst[S.doubles] (device); clk != 0: the record that decides, on the device, whether they are taken.  The
+// one place that knows whether the backend has kernels of its own
+int spectra_queue(rgpu_ctx* c, const double* U, const StepClock* clk, const SpecSet& S, double* dst) {
+#ifdef RGPU_TILED_MONITOR_SPECTRUM
+  return rgpu_tiled::launch_monitor_spectrum(c->stream, c->g, S, rgpu::options().spectrum_tile_y, U, c->montw.d, clk, c->F, dst);
+#else
+  const SpecBox b = spec_box(c->g);
+  const double N = (double)b.nx * (double)b.ny * (double)b.nz;
+  for (int m = 0; m < S.n; ++m) {
+    int ca[SPEC_NQ], cb[SPEC_NQ];
+    const int nt = spec_pairs(S.s[m].channels, ca, cb);
+    for (int t = 0; t < nt; ++t) {
+      K_mon_spectrum_x kx = {c->g, b, ca[t], cb[t], U, c->montw.d, c->F, clk};
+      K_mon_spectrum_line ky = {b, 1, c->montw.d, c->F, clk};
+      K_mon_spectrum_line kz = {b, 2, c->montw.d, c->F, clk};
+      K_mon_spectrum_bin kb = {b, S.s[m], t == 0 ? 1 : 0, 1.0 / (N * N), c->F, dst, clk};
+      if (rg_launch<kBlock>(c->stream, (unsigned)(b.ny * b.nz), kx) || rg_launch<kBlock>(c->stream, (unsigned)(b.nx * b.nz), ky) || rg_launch<kBlock>(c->stream, (unsigned)(b.nx * b.ny), kz) ||
+          rg_launch<kBlock>(c->stream, (unsigned)S.s[m].shells, kb))
+        return -1;
+    }
+  }
+  return 0;
+#endif
+}
+// one sample of U[parity] outside a batch, of a set that was not refused
+int spectra_take(rgpu_ctx* c, const std::string& who, int parity, const SpecSet& S, double* out) {
+  if (spectrum_log_reserve(c, S.doubles)) return RG_HIPFAIL(c, who + ": device buffer of the spectra");
+  if (spectra_queue(c, c->U[parity & 1], 0, S, c->mons.d) || rg_copy_d2h(out, c->mons.d, S.doubles * sizeof(double), c->stream) || rg_stream_sync(c->stream))
+    return RG_HIPFAIL(c, who);
+  return RGPU_OK;
+}
+int state_spectra(rgpu_ctx* c, int parity, int nspec, const rgpu_spectrum_spec* specs, double* out) {
+  RG_CHECK_CTX(c);
+  const std::string who = "state_spectra";
+  if (!out || !specs) return fail(c, RGPU_EINVAL, who + ": null pointer");
+  SpecSet S;
+  if (const int rc = spectra_refusal(c, who, nspec, specs, &S)) return rc;
+  return spectra_take(c, who, parity, S, out);
+}
+
+// ---- the samples of a batch: of the monitor, of the plane monitor, of the map monitor, of the PDF or of the spectrum monitor ---------
 // which sample a call takes (and, for maps and PDFs, of what).  Samples are 8-byte words, doubles or counts: the loop only copies them
-enum MonWhat { MON_MONITOR, MON_PLANES, MON_MAPS, MON_PDFS };
-struct MonSample { MonWhat what; int nmaps; const rgpu_map_spec* specs; const PdfSet* pdf; };
+enum MonWhat { MON_MONITOR, MON_PLANES, MON_MAPS, MON_PDFS, MON_SPECTRA };
+struct MonSample { MonWhat what; int nmaps; const rgpu_map_spec* specs; const PdfSet* pdf; const SpecSet* spec; };
 size_t monitor_sample_doubles(const rgpu_ctx* c, const MonSample& S) {
+  if (S.what == MON_SPECTRA) return (size_t)S.spec->doubles;
   if (S.what == MON_PDFS) return (size_t)S.pdf->words;
   return S.what == MON_MAPS ? maps_sample_doubles(c, S.nmaps, S.specs) : S.what == MON_PLANES ? monp_sample_doubles(c->g) : (size_t)MON_NQ;
 }
 // whether the samples of this context can be taken inside its device-clock batches.  Maps need no scratch: one sample within the
-// budget.  PDFs: their scratch was checked with the specs
+// budget.  PDFs and spectra: their scratch was checked with the specs
 bool monitor_sample_fits(rgpu_ctx* c, const MonSample& S) {
-  if (S.what == MON_PDFS) return true;
+  if (S.what == MON_PDFS || S.what == MON_SPECTRA) return true;
   if (S.what == MON_MAPS) return c->g.three_d && monitor_sample_doubles(c, S) <= map_log_budget_doubles();
   return S.what == MON_PLANES ? monitor_planes_scratch_fits(c) : monitor_scratch_fits(c);
 }
-DeviceMirror<double>& monitor_batch_log(rgpu_ctx* c, const MonSample& S) { return S.what == MON_PDFS ? c->monh : S.what == MON_MAPS ? c->monm : S.what == MON_PLANES ? c->monp : c->mon; }
+DeviceMirror<double>& monitor_batch_log(rgpu_ctx* c, const MonSample& S) { return S.what == MON_SPECTRA ? c->mons : S.what == MON_PDFS ? c->monh : S.what == MON_MAPS ? c->monm : S.what == MON_PLANES ? c->monp : c->mon; }
 // The slots of the log of a call that samples every `every` steps.  The monitor's: a slot per step of a batch.  The plane monitor's:
 // a slot per sample that can fall into one batch.  The maps': as many, or as the budget holds if that is fewer (at least one:
 // monitor_sample_fits)
 size_t monitor_batch_slots(const rgpu_ctx* c, const MonSample& S, int every) {
   if (S.what == MON_MONITOR) return (size_t)rgpu_ctx::kClockBatch;
   const size_t slots = (size_t)rgpu_ctx::kClockBatch / (size_t)every + 1;
-  if (S.what == MON_PLANES || S.what == MON_PDFS) return slots;   // (a PDF sample is at most 128 KiB: no byte budget)
+  if (S.what == MON_PLANES || S.what == MON_PDFS || S.what == MON_SPECTRA) return slots;   // (a PDF sample is at most 128 KiB, the spectra 256 KiB: no byte budget)
   const size_t held = map_log_budget_doubles() / monitor_sample_doubles(c, S);
   return held < slots ? held : slots;
 }
@@ -293,6 +406,7 @@ int monitor_batch_alloc(rgpu_ctx* c, const MonSample& S, int every) {
   const size_t n = slots * monitor_sample_doubles(c, S);
   if (S.what == MON_MAPS) return map_log_reserve(c, n);
   if (S.what == MON_PDFS) return pdf_log_reserve(c, n);
+  if (S.what == MON_SPECTRA) return spectrum_log_reserve(c, n);
   DeviceMirror<double>& log = monitor_batch_log(c, S);
   if (S.what == MON_PLANES && log.allocated() && c->monp_slots < slots) log.release();
   if (log.allocated()) return 0;
@@ -308,9 +422,9 @@ int monitor_batch_alloc(rgpu_ctx* c, const MonSample& S, int every) {
 int monitor_batch_queue(rgpu_ctx* c, const MonSample& S, int parity, int k) {
   double* dst = monitor_batch_log(c, S).d + (size_t)k * monitor_sample_doubles(c, S);
   const double* U = c->U[parity & 1];
-  const int rc = S.what == MON_PDFS ? pdfs_queue(c, U, c->clk_cur, *S.pdf, dst) : S.what == MON_MAPS ? maps_queue(c, U, c->clk_cur, S.nmaps, S.specs, dst)
+  const int rc = S.what == MON_SPECTRA ? spectra_queue(c, U, c->clk_cur, *S.spec, dst) : S.what == MON_PDFS ? pdfs_queue(c, U, c->clk_cur, *S.pdf, dst) : S.what == MON_MAPS ? maps_queue(c, U, c->clk_cur, S.nmaps, S.specs, dst)
                : S.what == MON_PLANES ? monitor_planes_queue(c, U, c->clk_cur, dst) : monitor_queue(c, U, c->clk_cur, dst);
-  if (rc == 0) ++(S.what == MON_PDFS ? c->monh_samples : S.what == MON_MAPS ? c->monm_samples : S.what == MON_PLANES ? c->monp_samples : c->mon_samples);
+  if (rc == 0) ++(S.what == MON_SPECTRA ? c->mons_samples : S.what == MON_PDFS ? c->monh_samples : S.what == MON_MAPS ? c->monm_samples : S.what == MON_PLANES ? c->monp_samples : c->mon_samples);
   return rc;
 }
 

@@ -1,4 +1,4 @@
-// api/run_steps.h -- entry points: the time loop of a lone context (rgpu_run_steps, _log, _history, _monitored, _monitored_planes, _mapped, _pdfs; every member-alone round
+// api/run_steps.h -- entry points: the time loop of a lone context (rgpu_run_steps, _log, _history, _monitored, _monitored_planes, _mapped, _pdfs, _spectra; every member-alone round
 // of an ensemble comes through here too).  One LoneRun per call; per turn either the reference's loop body (literal_turn) or a batch
 // of device-clock steps (api/entry_clock.h), queued by batch_queue and read back once by batch_harvest.  The two optional consumers
 // of a step -- the history row in front of it, the monitor sample behind it -- each write the caller's arrays in one place, put().
@@ -64,7 +64,8 @@ int literal_turn(LoneRun& run) {
   if (run.mon && run.mon->due(*run.nStep)) {
     const MonRun* M = run.mon;
     const int par = *run.nStep & 1;
-    if (const int rc = M->what.what == MON_PDFS ? pdfs_take(c, M->who, par, *M->what.pdf, M->slot())
+    if (const int rc = M->what.what == MON_SPECTRA ? spectra_take(c, M->who, par, *M->what.spec, M->slot())
+                     : M->what.what == MON_PDFS ? pdfs_take(c, M->who, par, *M->what.pdf, M->slot())
                      : M->what.what == MON_MAPS ? state_maps(c, par, M->what.nmaps, M->what.specs, M->slot())
                      : M->what.what == MON_PLANES ? state_monitor_planes(c, par, M->slot()) : state_monitor(c, c->g.three_d != 0, par, M->slot())) return rc;
     M->put(*run.nStep, *run.t);
@@ -219,7 +220,7 @@ int rgpu_run_steps_monitored(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, d
   if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, "run_steps_monitored: single-domain contexts only (a slab holds a part of the box)");
   if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_monitored: nsteps is negative");
   if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_monitored: every must be at least 1");
-  const MonRun M = {every, {MON_MONITOR, 0, 0, 0}, (size_t)RGPU_MON_NQ, mon_n, mon_step, mon_t, mon, "run_steps_monitored"};
+  const MonRun M = {every, {MON_MONITOR, 0, 0, 0, 0}, (size_t)RGPU_MON_NQ, mon_n, mon_step, mon_t, mon, "run_steps_monitored"};
   LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
   return run_steps_impl(run);
 }
@@ -237,7 +238,7 @@ int rgpu_run_steps_monitored_planes(rgpu_ctx* c, int nsteps, double tEnd, int* n
   if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: nsteps is negative");
   if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: every must be at least 1");
   if (!monitor_planes_scratch_fits(c)) return fail(c, RGPU_EINVAL, "run_steps_monitored_planes: no scratch for the partial sums");
-  const MonRun M = {every, {MON_PLANES, 0, 0, 0}, monp_sample_doubles(c->g), mon_n, mon_step, mon_t, mon, "run_steps_monitored_planes"};
+  const MonRun M = {every, {MON_PLANES, 0, 0, 0, 0}, monp_sample_doubles(c->g), mon_n, mon_step, mon_t, mon, "run_steps_monitored_planes"};
   LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
   return run_steps_impl(run);
 }
@@ -252,7 +253,7 @@ int rgpu_run_steps_mapped(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, doub
   if (const int rc = maps_refusal(c, "run_steps_mapped", nmaps, specs)) return rc;
   if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_mapped: nsteps is negative");
   if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_mapped: every must be at least 1");
-  const MonSample S = {MON_MAPS, nmaps, specs, 0};
+  const MonSample S = {MON_MAPS, nmaps, specs, 0, 0};
   const MonRun M = {every, S, monitor_sample_doubles(c, S), mon_n, mon_step, mon_t, maps, "run_steps_mapped"};
   LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
   return run_steps_impl(run);
@@ -269,8 +270,25 @@ int rgpu_run_steps_pdfs(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double
   if (const int rc = pdfs_refusal(c, "run_steps_pdfs", npdfs, specs, &set)) return rc;
   if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_pdfs: nsteps is negative");
   if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_pdfs: every must be at least 1");
-  const MonSample S = {MON_PDFS, 0, 0, &set};
+  const MonSample S = {MON_PDFS, 0, 0, &set, 0};
   const MonRun M = {every, S, (size_t)set.words, mon_n, mon_step, mon_t, reinterpret_cast<double*>(pdfs), "run_steps_pdfs"};
+  LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
+  return run_steps_impl(run);
+}
+
+long rgpu_spectrum_batch_samples(rgpu_ctx* c) { return c ? c->mons_samples : 0; }
+
+int rgpu_run_steps_spectra(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int every,
+                           int nspec, const rgpu_spectrum_spec* specs, int* mon_n, int* mon_step, double* mon_t, double* spectra) {
+  RG_CHECK_CTX(c);
+  if (mon_n) *mon_n = 0;
+  if (!nStep || !t || !dt || !specs || !mon_n || !mon_step || !mon_t || !spectra) return fail(c, RGPU_EINVAL, "run_steps_spectra: null pointer");
+  SpecSet set;
+  if (const int rc = spectra_refusal(c, "run_steps_spectra", nspec, specs, &set)) return rc;
+  if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_spectra: nsteps is negative");
+  if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_spectra: every must be at least 1");
+  const MonSample S = {MON_SPECTRA, 0, 0, 0, &set};
+  const MonRun M = {every, S, (size_t)set.doubles, mon_n, mon_step, mon_t, spectra, "run_steps_spectra"};
   LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
   return run_steps_impl(run);
 }

@@ -25,3 +25,6 @@
 #include "monitor_pdf.h"
 // the gfx950 kernels of the PDF monitor exist (api/monitor.h: without this macro it runs the flat functors)
 #define RGPU_TILED_MONITOR_PDF 1
+#include "monitor_spectrum.h"
+// the gfx950 kernels of the spectrum monitor exist (api/monitor.h: without this macro it runs the flat functors)
+#define RGPU_TILED_MONITOR_SPECTRUM 1

@@ -973,6 +973,104 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     if (!f) throw std::runtime_error("cannot write " + pdfs_list);
     f << "# nStep totalTime pdf spec file\n";
   }
+  // [spectra] enabled=yes every=N spectrum0="w 1 1 1" spectrum1="b 4 1 4" ... (up to spectrum3, numbered from 0 without a gap):
+  // shell-binned power spectra of a 3D single-domain run whose extents are powers of two (include/rgpu.h, "spectrum monitors") after
+  // every step that brings nStep to a multiple of `every`.  A spec is "<channels> <wx> <wy> <wz>": the channels names of
+  // RGPU_SPECTRUM_NAMES or the shorthands v, w, b, m (all three components) joined by commas, then the three integer weights.  Each
+  // sample of each spec is one file <outputDir>/<outputPrefix>_spectrum<m>_<step, 7 digits>.npy -- NumPy format 1.0, '<f8', C order,
+  // shape (2, S): the power, then the modes of each shell -- and one line "step t spectrum spec file" of <outputPrefix>_spectra.txt,
+  // t with 17 significant digits.  Driven as [pdfs] is; a batch serves one consumer, and the spectra take the batches where neither
+  // the maps nor the PDFs do.  Not for z-slab, hooked or 2D runs, nor for a box with an extent that is no power of two in 4 .. 1024:
+  // noted once, the run goes on.
+  const bool spectraEnabled = cfg_.get_bool("spectra", "enabled", false);
+  const int spectra_every = spectraEnabled ? (int)cfg_.get_integer("spectra", "every", 10) : 0;
+  if (spectraEnabled && spectra_every < 1) throw std::runtime_error("[spectra] every must be at least 1");
+  bool noted_spectra = false;
+  const auto pow2_extent = [](int n) { return n >= 4 && n <= 1024 && (n & (n - 1)) == 0; };
+  const bool spectra_box = !slab() && !hooked_ && p_.nz_global != 1 && pow2_extent(p_.nx) && pow2_extent(p_.ny) && pow2_extent(p_.nz);
+  if (spectraEnabled && !spectra_box)
+    note_once(&noted_spectra, p_.nz_global == 1 ? "2D run: the spectrum files are not written" : (slab() || hooked_) ? "z-slab run: the spectrum files are not written"
+                                                                                                 : "an extent of the box is not a power of two in 4 .. 1024: the spectrum files are not written");
+  std::vector<rgpu_spectrum_spec> spectrum_specs;
+  std::vector<std::string> spectrum_texts;
+  std::vector<size_t> spectrum_at(1, 0);   // spec m of a sample begins at spectrum_at[m]; spectrum_at.back(): the doubles of a sample
+  if (spectraEnabled && spectra_box) {
+    // the mask of "<channels>"; 0: not a list of channels
+    const auto parse_channels = [](const std::string& text) {
+      unsigned mask = 0;
+      for (size_t at = 0; at <= text.size();) {
+        const size_t comma = text.find(',', at);
+        const std::string one = text.substr(at, comma == std::string::npos ? comma : comma - at);
+        std::istringstream names(RGPU_SPECTRUM_NAMES);
+        std::string name;
+        unsigned hit = 0;
+        for (int q = 0; names >> name; ++q)
+          if (name == one || (one.size() == 1 && name.size() == 2 && name[0] == one[0] && std::string("vwbm").find(one[0]) != std::string::npos)) hit |= 1u << q;
+        if (!hit) return 0u;
+        mask |= hit;
+        if (comma == std::string::npos) break;
+        at = comma + 1;
+      }
+      return mask;
+    };
+    for (int m = 0; m < RGPU_SPECTRUM_MAX; ++m) {
+      const std::string key = "spectrum" + std::to_string(m);
+      std::string text = cfg_.get_string("spectra", key, "");
+      if (text.empty()) break;
+      if (text.size() >= 2 && text.front() == '"' && text.back() == '"') text = text.substr(1, text.size() - 2);
+      std::istringstream in(text);
+      std::string channels, rest;
+      rgpu_spectrum_spec sp = {};
+      const bool ok = static_cast<bool>(in >> channels >> sp.wx >> sp.wy >> sp.wz) && !(in >> rest) && (sp.channels = parse_channels(channels)) != 0;
+      const int shells = ok ? rgpu_spectrum_shells(ctx_, &sp) : 0;
+      if (shells == 0)
+        throw std::runtime_error("[spectra] " + key + "=" + text + ": expected \"<channels> <wx> <wy> <wz>\" (channels of \"" RGPU_SPECTRUM_NAMES "\" or v, w, b, m, joined by commas; weights 0 .. " +
+                                 std::to_string(RGPU_SPECTRUM_MAX_WEIGHT) + ", not all zero; at most " + std::to_string(RGPU_SPECTRUM_MAX_SHELLS) + " shells)");
+      spectrum_specs.push_back(sp);
+      std::string word = text;   // (one word in the list: the blanks become colons)
+      for (char& ch : word) if (ch == ' ' || ch == '\t') ch = ':';
+      spectrum_texts.push_back(word);
+      spectrum_at.push_back(spectrum_at.back() + 2 * (size_t)shells);
+    }
+  }
+  const bool spectra_on = !spectrum_specs.empty();
+  const std::string spectra_list = rs_.outputDir + "/" + rs_.outputPrefix + "_spectra.txt";
+  // n samples of all spectra: the .npy files and their lines in the list
+  const auto spectra_files = [&](int n, const int* step, const double* t, const double* v) {
+    std::ofstream list(spectra_list.c_str(), std::ios::app);
+    if (!list) throw std::runtime_error("cannot write " + spectra_list);
+    char num[64];
+    for (int k = 0; k < n; ++k)
+      for (size_t m = 0; m < spectrum_specs.size(); ++m) {
+        std::snprintf(num, sizeof(num), "_spectrum%d_%07d.npy", (int)m, step[k]);
+        const std::string name = rs_.outputPrefix + num, path = rs_.outputDir + "/" + name;
+        const size_t doubles = spectrum_at[m + 1] - spectrum_at[m];
+        // NumPy format 1.0, as the maps' files: the header padded with spaces to a multiple of 64
+        std::string head = "{'descr': '<f8', 'fortran_order': False, 'shape': (2, " + std::to_string(doubles / 2) + "), }";
+        head.append(63 - (10 + head.size()) % 64, ' ');
+        head += "\n";
+        std::ofstream f(path.c_str(), std::ios::binary | std::ios::trunc);
+        const char magic[10] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0, (char)(head.size() & 0xff), (char)(head.size() >> 8)};
+        f.write(magic, 10);
+        f.write(head.data(), (std::streamsize)head.size());
+        f.write(reinterpret_cast<const char*>(v + (size_t)k * spectrum_at.back() + spectrum_at[m]), (std::streamsize)(doubles * sizeof(double)));
+        if (!f) throw std::runtime_error("cannot write " + path);
+        std::snprintf(num, sizeof(num), " %.17g", t[k]);
+        list << step[k] << num << " " << m << " " << spectrum_texts[m] << " " << name << "\n";
+      }
+  };
+  std::vector<double> spectra_v, spectra_t;
+  std::vector<int> spectra_step;
+  const auto spectra_direct = [&](int n) {   // the spectra of the current state U[n % 2]
+    spectra_v.resize(std::max(spectra_v.size(), spectrum_at.back()));
+    check(rgpu_state_spectra(ctx_, n % 2, (int)spectrum_specs.size(), spectrum_specs.data(), spectra_v.data()), "state_spectra");
+    spectra_files(1, &n, &totalTime_, spectra_v.data());
+  };
+  if (spectra_on && !(totalTime_ > 0)) {   // the start of a run
+    std::ofstream f(spectra_list.c_str(), std::ios::trunc);
+    if (!f) throw std::runtime_error("cannot write " + spectra_list);
+    f << "# nStep totalTime spectrum spec file\n";
+  }
   const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   while (totalTime_ < rs_.tEnd && nStep < rs_.nStepmax) {
     if (rs_.nLog > 0 && (nStep % rs_.nLog) == 0 && p_.slab_rank == 0)
@@ -1006,12 +1104,23 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     // a batch serves one consumer: where the maps take it, the monitor rows come from the direct calls
     const bool maps_batched = maps_on && !historyEnabled && quiet > 1;
     const bool pdfs_batched = pdfs_on && !historyEnabled && quiet > 1 && !maps_batched;
-    const bool monitor_batched = monitor_on && !historyEnabled && quiet > 1 && !maps_batched && !pdfs_batched;
+    const bool spectra_batched = spectra_on && !historyEnabled && quiet > 1 && !maps_batched && !pdfs_batched;
+    const bool monitor_batched = monitor_on && !historyEnabled && quiet > 1 && !maps_batched && !pdfs_batched && !spectra_batched;
     if (monitor_on && !monitor_batched && mon_every - nStep % mon_every < quiet) quiet = mon_every - nStep % mon_every;   // the direct call follows
     if (maps_on && !maps_batched && maps_every - nStep % maps_every < quiet) quiet = maps_every - nStep % maps_every;      // the direct call follows
     if (pdfs_on && !pdfs_batched && pdfs_every - nStep % pdfs_every < quiet) quiet = pdfs_every - nStep % pdfs_every;      // the direct call follows
+    if (spectra_on && !spectra_batched && spectra_every - nStep % spectra_every < quiet) quiet = spectra_every - nStep % spectra_every;   // the direct call follows
     const int nStep_before = nStep;
-    if (pdfs_batched) {
+    if (spectra_batched) {
+      int mn = 0;
+      const size_t cap = (size_t)(quiet / spectra_every + 1);
+      if (spectra_step.size() < cap) { spectra_step.resize(cap); spectra_t.resize(cap); }
+      if (spectra_v.size() < cap * spectrum_at.back()) spectra_v.resize(cap * spectrum_at.back());
+      const int rc = rgpu_run_steps_spectra(ctx_, quiet, rs_.tEnd, &nStep, &totalTime_, &dt, 0, spectra_every, (int)spectrum_specs.size(), spectrum_specs.data(), &mn, spectra_step.data(), spectra_t.data(),
+                                            spectra_v.data());
+      spectra_files(mn, spectra_step.data(), spectra_t.data(), spectra_v.data());
+      if (rc < 0) check(rc, "run_steps_spectra");
+    } else if (pdfs_batched) {
       int mn = 0;
       const size_t cap = (size_t)(quiet / pdfs_every + 1);
       if (pdfs_step.size() < cap) { pdfs_step.resize(cap); pdfs_t.resize(cap); }
@@ -1062,6 +1171,7 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     if (monitor_on && !monitor_batched && nStep > nStep_before && nStep % mon_every == 0) monitor_direct(nStep);
     if (maps_on && !maps_batched && nStep > nStep_before && nStep % maps_every == 0) maps_direct(nStep);
     if (pdfs_on && !pdfs_batched && nStep > nStep_before && nStep % pdfs_every == 0) pdfs_direct(nStep);
+    if (spectra_on && !spectra_batched && nStep > nStep_before && nStep % spectra_every == 0) spectra_direct(nStep);
   }
   check(rgpu_synchronize(ctx_), "synchronize");
   if (hooked_) hook_check(hooks_.barrier(hooks_.self), "barrier");

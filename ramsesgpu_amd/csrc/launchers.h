@@ -11,6 +11,7 @@
 #include "kernels_monitor_planes.h"   // the plane monitor: sixteen columns per interior plane, on the monitor's terms and order
 #include "kernels_monitor_maps.h"     // the map monitor: twelve channels per pixel, slices and sums along an axis, on the same terms
 #include "kernels_monitor_pdf.h"      // the PDF monitor: counts per class of thirteen channels, 1D and joint, on the same terms
+#include "kernels_monitor_spectrum.h" // the spectrum monitor: shell-binned power of thirteen channels, line transforms in three passes
 #include "rg_options.h"        // option spec (hydro_pick_spec)
 #include "step_clock_rec.h"   // StepClock: the time step as a device record (kernels with a `clk` member read it instead of their by-value arguments)
 

@@ -20,6 +20,7 @@ struct Options {
   int map_x_tiled = -1;   // the kernel that sums a map along x (hip/monitor_maps.h): -1 by the thickness of the range, 0 direct, 1 tiled
   int pdf_replicas = -1;  // copies of the LDS table of the PDF monitor's count kernel (hip/monitor_pdf.h): -1 automatic, n forces the count (the same words)
   int pdf_groups = -1;    // workgroups of that kernel: -1 automatic, n forces the grid size (the same words)
+  int spectrum_tile_y = -1;   // log2 of the lines a tile of the spectrum monitor's y pass holds (hip/monitor_spectrum.h): -1 the widest that fits, 0 .. 6 (the same doubles)
 };
 inline Options& options() { static Options o; return o; }
 inline int* option_slot(const char* name) {
@@ -37,6 +38,7 @@ inline int* option_slot(const char* name) {
   if (!std::strcmp(name, "map_x_tiled")) return &o.map_x_tiled;
   if (!std::strcmp(name, "pdf_replicas")) return &o.pdf_replicas;
   if (!std::strcmp(name, "pdf_groups")) return &o.pdf_groups;
+  if (!std::strcmp(name, "spectrum_tile_y")) return &o.spectrum_tile_y;
   return 0;
 }
 

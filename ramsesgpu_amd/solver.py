@@ -23,6 +23,58 @@ MonitorSeries = collections.namedtuple("MonitorSeries", "step t values")
 MapSeries = collections.namedtuple("MapSeries", "step t maps")
 # the series out of run_steps_pdfs: step numbers [n], times [n], and per spec an array of uint64 [n, na + 3] or [n, na + 3, nb + 3]
 PdfSeries = collections.namedtuple("PdfSeries", "step t pdfs")
+# the series out of run_steps_spectra: step numbers [n], times [n], and per spec the power [n, S] and the mode counts [n, S]
+SpectrumSeries = collections.namedtuple("SpectrumSeries", "step t power modes")
+# the shorthands of a spec's channels
+SPECTRUM_GROUPS = {"v": ("vx", "vy", "vz"), "w": ("wx", "wy", "wz"), "b": ("bx", "by", "bz"), "m": ("mx", "my", "mz")}
+
+
+def spectrum_spec(spec):
+    """a spec of a spectrum as _capi.RgpuSpectrumSpec, from one, or from (channels, (wx, wy, wz)) -- the channels one name or several of
+    _capi.SPECTRUM_NAMES or of the shorthands "v", "w", "b", "m" (all three components), or the bit mask itself"""
+    if isinstance(spec, _capi.RgpuSpectrumSpec):
+        return spec
+    channels, weights = spec
+    if isinstance(channels, int):
+        mask = channels
+    else:
+        mask = 0
+        for name in ((channels,) if isinstance(channels, str) else channels):
+            for ch in SPECTRUM_GROUPS.get(name, (name,)):
+                mask |= 1 << _capi.SPECTRUM_NAMES.index(ch)
+    wx, wy, wz = (int(w) for w in weights)
+    return _capi.RgpuSpectrumSpec(mask, wx, wy, wz)
+
+
+def spectrum_shells(shape, weights):
+    """(S, M) of the weights (wx, wy, wz) on a box of shape (nx, ny, nz), from the integer rule of include/rgpu.h ("spectrum monitors")
+    without a context: the number of shells and the modes of each, numpy.int64 [S].  Shell s holds the q = (wx kx)^2 + (wy ky)^2 +
+    (wz kz)^2 with s^2 - s + 1 <= q <= s^2 + s, the wave numbers folded to -n / 2 .. n / 2 - 1"""
+    q1 = []
+    for n, w in zip(shape, weights):
+        k = np.arange(int(n), dtype=np.int64)
+        q1.append((int(w) * np.minimum(k, int(n) - k)) ** 2)
+    shell = lambda q: (lambda r: np.where(q <= r * r + r, r, r + 1))(_isqrt(q))
+    S = int(shell(np.array([sum(int(a.max()) for a in q1)], dtype=np.int64))[0]) + 1
+    M = np.zeros(S, dtype=np.int64)
+    # the modes (kx, ky) by their distinct q, then one pass over kz per distinct value
+    vx, cx = np.unique(q1[0], return_counts=True)
+    vy, cy = np.unique(q1[1], return_counts=True)
+    vz, cz = np.unique(q1[2], return_counts=True)
+    flat = (vx[:, None] + vy[None, :]).ravel()
+    order = np.argsort(flat, kind="stable")
+    qxy, start = np.unique(flat[order], return_index=True)
+    cxy = np.add.reduceat((cx[:, None] * cy[None, :]).ravel()[order], start)
+    for q, c in zip(vz, cz):
+        np.add.at(M, shell(qxy + q), cxy * c)
+    return S, M
+
+
+def _isqrt(q):
+    """floor(sqrt(q)) of non-negative int64, exact: the rounded root put right in integers"""
+    r = np.floor(np.sqrt(q.astype(np.float64))).astype(np.int64)
+    r = np.where(r * r > q, r - 1, r)
+    return np.where((r + 1) * (r + 1) <= q, r + 1, r)
 
 
 def pdf_axis(axis):
@@ -427,6 +479,46 @@ class Solver:
             self._chk(done, "run_steps_pdfs")
         self.dt_log = [log[i] for i in range(done)]
         return done, self.pdf_series
+
+    def _spectrum_specs(self, specs):
+        """specs as spectrum_spec takes them -> (the C array, the shells of each on this context; 0 where the library refuses it)"""
+        arr = (_capi.RgpuSpectrumSpec * max(len(specs), 1))()
+        for m, spec in enumerate(specs):
+            arr[m] = spectrum_spec(spec)
+        return arr, [int(self.lib.rgpu_spectrum_shells(self.ctx, C.byref(arr[m]))) for m in range(len(specs))]
+
+    def state_spectra(self, specs, parity=None):
+        """shell-binned power spectra of U[parity] (default: nStep % 2) of a 3D state whose extents are powers of two, the box taken as
+        periodic: a list, per spec, of (P, M) -- the power and the number of modes of each shell, numpy.float64 [S] (rgpu_state_spectra;
+        include/rgpu.h, "spectrum monitors").  A spec is (channels, (wx, wy, wz)), see spectrum_spec"""
+        arr, shells = self._spectrum_specs(specs)
+        out = np.zeros(max(2 * sum(shells), 1))
+        par = self.nStep % 2 if parity is None else int(parity)
+        self._chk(self.lib.rgpu_state_spectra(self.ctx, par, len(specs), arr, out.ctypes.data_as(_capi.c_double_p)), "state_spectra")
+        cuts = np.cumsum([0] + [2 * s for s in shells])
+        return [(out[cuts[m]:cuts[m] + shells[m]].copy(), out[cuts[m] + shells[m]:cuts[m + 1]].copy()) for m in range(len(specs))]
+
+    def run_steps_spectra(self, nsteps, every, specs, tEnd=float("inf")):
+        """run_steps with a sample of the spectra `specs` after every step that brings nStep to a multiple of `every`
+        (rgpu_run_steps_spectra: inside the device-clock batches the transforms run on the device, one read-back per batch).  Returns
+        (done, SpectrumSeries): the steps done and the samples of this call -- .step [n], .t [n] (the time after that step), .power and
+        .modes lists per spec of numpy.float64 [n, S]"""
+        arr, shells = self._spectrum_specs(specs)
+        cap = max(int(nsteps), 0) // max(int(every), 1) + 1
+        n, t, d, mn = C.c_int(self.nStep), C.c_double(self.totalTime), C.c_double(self.dt), C.c_int(0)
+        log = (C.c_double * max(int(nsteps), 1))()
+        mstep, mt, mv = np.zeros(cap, dtype=np.intc), np.zeros(cap), np.zeros((cap, max(2 * sum(shells), 1)))
+        done = self.lib.rgpu_run_steps_spectra(self.ctx, int(nsteps), float(tEnd), C.byref(n), C.byref(t), C.byref(d), log, int(every), len(specs), arr, C.byref(mn),
+                                               mstep.ctypes.data_as(C.POINTER(C.c_int)), mt.ctypes.data_as(_capi.c_double_p), mv.ctypes.data_as(_capi.c_double_p))
+        k = mn.value
+        self.nStep, self.totalTime, self.dt = n.value, t.value, d.value   # (they describe the steps that ran, also when the call failed)
+        cuts = np.cumsum([0] + [2 * s for s in shells])
+        self.spectrum_series = SpectrumSeries(mstep[:k].astype(int), mt[:k].copy(), [mv[:k, cuts[m]:cuts[m] + shells[m]].copy() for m in range(len(specs))],
+                                              [mv[:k, cuts[m] + shells[m]:cuts[m + 1]].copy() for m in range(len(specs))])
+        if done < 0:
+            self._chk(done, "run_steps_spectra")
+        self.dt_log = [log[i] for i in range(done)]
+        return done, self.spectrum_series
 
     def history_turbulence(self, nStep=None):
         """history_turbulence (MHDRunBase.cpp:3626-3810) reduced on the device: the 18 columns after totalTime and dt"""
