@@ -340,7 +340,13 @@ int rgpu_one_step_integration(rgpu_ctx* c, int* nStep, double* t, double* dt);
  * loop condition and t += dt evaluated by a one-workgroup kernel between two steps) and a batch of steps is queued without a host round
  * trip -- at the shipped 2D sizes that round trip costs as much as a third of the step.  Since round 5 the 3D steps do the same (hydro,
  * plain / shearing-box MHD through the z-marching sweeps: rgpu_clock_capable; a rotating box with periodic x faces leaves no CFL maxima
- * behind -- the reference scans its refilled ghosts -- and runs the plain loop).  Every other configuration runs the plain loop. */
+ * behind -- the reference scans its refilled ghosts -- and runs the plain loop).  Driven turbulence -- a lone, non-rotating 3D context
+ * with random forcing, Ornstein-Uhlenbeck forcing or both, no gravity, no dissipative stage, phase timers off -- is batched too (option
+ * "forcing_clock"): the sums and the norm of the random forcing and the mode step of the Ornstein-Uhlenbeck process are formed on the
+ * device with the host's expressions, from deviates the host draws ahead, and the last kick of a step carries the CFL scan of the
+ * state it leaves; a state without CFL maxima in the slots (the first step of a run, the state a single step left) gets its scan
+ * queued and the batch opens.  States, dt sequence and the process (rgpu_ou_forcing_get_state, generator included) are the plain
+ * loop's, bit for bit.  Every other configuration runs the plain loop. */
 int rgpu_run_steps(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt);
 /* ... the same, and dt_log[n] = the time step of the n-th step done (the "dt=" column of the reference's log, MHDRunGodunov.cpp:3958);
  * dt_log holds nsteps doubles or is NULL.  If a launch fails after some steps of a batch were queued, *nStep, *t, *dt (and dt_log)
@@ -380,15 +386,22 @@ int rgpu_run_steps_history(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, dou
 /* how many heads of rgpu_run_steps_history this context has queued on the device so far (one per step of a device-clock batch,
  * sampling or not; 0 where every call took the literal loop): lets a caller (and the tests) tell which path ran */
 long rgpu_history_batch_heads(rgpu_ctx* c);
+/* how many steps of this context ran inside device-clock batches of rgpu_run_steps* with a forcing stage queued behind their core (random
+ * or Ornstein-Uhlenbeck forcing, option "forcing_clock"; 0 where every forced step took the literal loop): which path ran, as above */
+long rgpu_forcing_batch_steps(rgpu_ctx* c);
 /* 1 when the next step of rgpu_run_steps on the state U[parity] would take its time step from the device (see above), else 0:
- * lets a caller (and the tests) tell which loop runs. */
+ * lets a caller (and the tests) tell which loop runs.  A forced context (see rgpu_run_steps): 1 for a state that came out of a batch --
+ * its CFL maxima are in the slots, the next rgpu_compute_dt fetches them and does not scan; 0 after a single step, and always with
+ * option "forcing_clock" = 0. */
 int rgpu_device_time_step_ready(rgpu_ctx* c, int parity);
 
 /* The device-side time step as pieces, for a driver that queues whole batches of steps itself (the z-slab driver: all-reduce of the
  * 1/dt slots in place -> clock -> step pieces -> halo exchange, no host turn between steps; rgpu_run_steps is built on the same three).
  *   rgpu_clock_capable  1 when every kernel of this context's step that depends on dt or t can read them from a device record
  *                       (csrc/step_clock_rec.h): 2D fused steps; 3D hydro and MHD through the z-marching sweeps, incl. the rotating frame
- *                       and the shearing box (periodic y); no gravity, dissipative stage, forcing, phase timers.
+ *                       and the shearing box (periodic y); no gravity, dissipative stage, forcing, phase timers.  (Forcing: the pieces
+ *                       below include no forcing stage, so a forced context answers 0 here and rgpu_clock_open refuses it; the library's
+ *                       own loop, rgpu_run_steps*, queues the forcing stages itself and batches such a context all the same.)
  *   rgpu_clock_open     starts a batch at time t0; steps stop being executed once t >= tEnd (HUGE_VAL: never).
  *   rgpu_clock_tick     queues the clock kernel of the NEXT step: folds the RGPU_DT_SLOTS device slots (which must hold the CFL maxima of
  *                       the step's input state -- all-reduced across slabs by the caller), zeroes them for the step's own scan, forms
@@ -576,7 +589,8 @@ int rgpu_ensemble_run_steps(rgpu_ensemble* e, int nsteps, const double* tEnd, in
  *                          host knows the step number, only "did the step run" comes from the record, which on small 2D hydro grids is
  *                          written by that step's own kernel -- and write to a device log of RGPU_CLOCK_BATCH slots that is copied back
  *                          once per batch with the clock records: no synchronisation inside a batch.  Everywhere else (first steps,
- *                          gravity, the dissipative stage, forcing, a rotating 2D box, phase timers, option "step_clock" = 0) the call
+ *                          gravity, the dissipative stage, forcing with option "forcing_clock" = 0,
+ *                          a rotating 2D box, phase timers, option "step_clock" = 0) the call
  *                          is the literal loop: rgpu_one_step_integration, then rgpu_state_monitor / rgpu_state_monitor3d.
  *                          Partial sums go to the flux array, dead between steps; the log (RGPU_CLOCK_BATCH x RGPU_MON_NQ doubles)
  *                          and its pinned mirror are allocated by the first call that needs them, freed with the context, and
@@ -638,7 +652,8 @@ long rgpu_monitor_batch_samples(rgpu_ctx* c);
  *                          sample (csrc/hip/monitor_profile.h) are queued behind the last kernel of each qualifying step, return in
  *                          their first instructions when the step's clock record says stop, and write to a device log that is copied
  *                          back once per batch with the clock records: no synchronisation inside a batch.  Everywhere else (first
- *                          steps, gravity, the dissipative stage, forcing, phase timers, option "step_clock" = 0) the call is the
+ *                          steps, gravity, the dissipative stage, forcing with option "forcing_clock" = 0,
+ *                          phase timers, option "step_clock" = 0) the call is the
  *                          literal loop: rgpu_one_step_integration, then rgpu_state_monitor_planes.  A call samples the monitor or
  *                          the planes, not both: the monitor's columns are the fold of the rows (the identity above).
  *                          Memory: the partial sums (RGPU_MONP_NQ x nz x ceil(ny / RGPU_MON_ROWS) x nx doubles, then the nz rows of
@@ -700,7 +715,8 @@ long rgpu_monitor_planes_batch_samples(rgpu_ctx* c);
  *                          sample (csrc/hip/monitor_maps.h) are queued behind the last kernel of each qualifying step, return in
  *                          their first instructions when the step's clock record says stop, and write to a device log that is copied
  *                          back once per batch with the clock records: no synchronisation inside a batch.  Everywhere else (first
- *                          steps, gravity, the dissipative stage, forcing, phase timers, option "step_clock" = 0) the call is the
+ *                          steps, gravity, the dissipative stage, forcing with option "forcing_clock" = 0,
+ *                          phase timers, option "step_clock" = 0) the call is the
  *                          literal loop: rgpu_one_step_integration, then rgpu_state_maps.
  *                          Memory: maps need no scratch, the flux array is not used.  The log of a batch has a byte budget, option
  *                          "map_log_kib" (default 262144: 256 MiB on the device and as much pinned): slots = min(RGPU_CLOCK_BATCH /
@@ -773,7 +789,8 @@ long rgpu_map_batch_samples(rgpu_ctx* c);
  *                          sample are queued behind the last kernel of each qualifying step, return in their first instructions when
  *                          the step's clock record says stop, and store to a device log that is copied back once per batch with the
  *                          clock records: no synchronisation inside a batch, no zeroing of the log.  Everywhere else (first steps,
- *                          gravity, the dissipative stage, forcing, phase timers, option "step_clock" = 0) the call is the literal
+ *                          gravity, the dissipative stage, forcing with option "forcing_clock" = 0,
+ *                          phase timers, option "step_clock" = 0) the call is the literal
  *                          loop: rgpu_one_step_integration, then rgpu_state_pdfs.  The log has RGPU_CLOCK_BATCH / every + 1 slots
  *                          (a sample is at most 128 KiB), is allocated by the first call that needs it, grown between batches if a
  *                          later call needs more, freed with the context, and is not part of rgpu_device_bytes.
@@ -915,6 +932,7 @@ int rgpu_selftest_alfven(const rgpu_params* p, int n, const double* states36, do
  *   "zseg" (0)          planes per z segment of the tiled sweeps; 0: planned per launch
  *   "chunks" (-1)       chunks of the two-stream schedule of the flat 3D MHD kernels, read by rgpu_create; 1: one stream
  *   "history_batch" (1) rgpu_run_steps_history samples on the device inside the device-clock batches; 0: its literal loop everywhere
+ *   "forcing_clock" (1) rgpu_run_steps* batch a lone 3D context with random / Ornstein-Uhlenbeck forcing; 0: its literal loop
  *   "member_params" (0) 1: the fused rounds of EVERY ensemble read their constants from the per-member table (the path of a
  *                       parameter scan), even when all sets are equal: the table path and the by-value path on one workload
  *   "map_log_kib" (262144) byte budget, in KiB, of the device log of the maps a batch of rgpu_run_steps_mapped samples ("map monitors")

@@ -121,6 +121,15 @@ struct rgpu_ctx {
   DeviceMirror<double> mons, montw;
   size_t mons_doubles = 0;
   long mons_samples = 0;        // spectrum samples queued on the device inside batches so far (rgpu_spectrum_batch_samples)
+  // the forcing stages inside a batch (api/forcing.h: forcing_batch_step; option "forcing_clock"), allocated by the first batch that needs
+  // them.  frc_norm: the norm of the random forcing, formed and read on the device.  ou_tab: the process as the kernels see it -- mode,
+  // force (an OuModes) and proj, kOuTab doubles -- uploaded from c->ou when ou_stale says that the host's copy is the newer one (creation,
+  // a literal step, rgpu_ou_forcing_set_state); its force comes back with the records of a batch.  ou_gauss: the deviates of the steps
+  // of a batch, one row of OuProcess::STEP_DEVIATES per slot, drawn ahead by the host and uploaded once per batch
+  enum { kOuTab = 2 * rgpu_ou::NDIM * rgpu_ou::NMODE + rgpu_ou::NDIM * rgpu_ou::NDIM * rgpu_ou::NMODE };
+  DeviceMirror<double> frc_norm, ou_tab, ou_gauss;
+  bool ou_stale = true;
+  long forcing_steps = 0;       // steps that ran inside batches with a forcing stage queued (rgpu_forcing_batch_steps)
   // fused 2D steps: the clock is folded into the step kernel itself (step_clock_rec.h: ClockFold) over three rotating slot arrays;
   // d_red always points at the array that holds the maxima of the current state
   unsigned long long* d_red_base = 0;   // 3 x RG_DT_SLOTS

@@ -6,7 +6,9 @@ extern "C" {
 // Configuration: every kernel of the step that depends on dt or t reads the record, and nothing in the step needs the host between
 // two steps.  2D: the fused step kernels (which also leave the ghost cells of their output: clock_ready).  3D: the z-marching
 // sweeps, the MHD update, the shear remap and the fused ghost fill.  Not with gravity ((0.5 dt) g travels in DevParams), the
-// dissipative stage, the forcings, the 2D rotating frame, the 2D jet, or the phase timers (they synchronise every launch anyway).
+// dissipative stage, the 2D rotating frame, the 2D jet, or the phase timers (they synchronise every launch anyway).  The forcings: not
+// for a batch opened from outside (the slab driver and other external drivers queue the step pieces themselves and queue no forcing
+// stage) -- the library's own loop queues them behind the core, reading the record (loop_config_ok below; api/forcing.h).
 static bool clock_config_ok(rgpu_ctx* c) {
   const rgpu_params& p = c->p;
   if (c->timers_on || p.gravityEnabled != 0 || p.nu > 0 || (p.mhdEnabled && p.eta > 0) || p.randomForcingEnabled || p.ouForcingEnabled) return false;
@@ -18,9 +20,11 @@ static bool clock_config_ok(rgpu_ctx* c) {
   FillXY f;
   return !(c->g.rot && c->g.shearbox) || fill_xy_plan(c, 0.0, 0.0, &f);   // the shearing ghost fill reads the record in its fused form only
 }
+// what rgpu_run_steps* batch: the above, and the forced 3D contexts of forcing_clock_ok (option "forcing_clock")
+static bool loop_config_ok(rgpu_ctx* c) { return clock_config_ok(c) || forcing_clock_ok(c); }
 // ... and the state U[parity]: its CFL maxima sit in the device slots; 2D: its ghost cells are the ones its kernel wrote
 static bool clock_ready(rgpu_ctx* c, int parity) {
-  if (c->p.slab_count != 1 || !clock_config_ok(c) || !c->rec.slots(parity)) return false;
+  if (c->p.slab_count != 1 || !loop_config_ok(c) || !c->rec.slots(parity)) return false;
   return c->g.three_d || (c->rec.slots(parity) == RG_DT_SLOTS && c->rec.ghosts_valid(parity));
 }
 static ClockConst clock_const(const rgpu_ctx* c) {
@@ -47,7 +51,7 @@ static int clock_open(rgpu_ctx* c, double t0, double tEnd, bool may_fold) {
   RG_CHECK_CTX(c);
   if (!c->U[0]) return fail(c, RGPU_EINVAL, "context was not created");
   if (c->clk_n >= 0) return fail(c, RGPU_EINVAL, "clock_open: a batch is already open");
-  if (!clock_config_ok(c)) return fail(c, RGPU_EUNSUPPORTED, "clock_open: this configuration takes its time step from the host");
+  if (!(may_fold ? loop_config_ok(c) : clock_config_ok(c))) return fail(c, RGPU_EUNSUPPORTED, "clock_open: this configuration takes its time step from the host");
   if (!c->clk.allocated() && c->clk.alloc(rgpu_ctx::kClockBatch)) return RG_HIPFAIL(c, "clock_open: records");
   c->clk_n = 0; c->clk_t0 = t0; c->clk_tEnd = tEnd; c->clk_cur = 0;
   // The clock folded into the step kernel itself (ClockFold): the fused 2D HYDRO step on grids of at most two rounds of resident

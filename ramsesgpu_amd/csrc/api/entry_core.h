@@ -91,6 +91,7 @@ int rgpu_ou_forcing_set_state(rgpu_ctx* c, const double* state) {
   RG_CHECK_CTX(c);
   if (!c->ou || !state) return fail(c, RGPU_EINVAL, "ou_forcing_set_state: no forcing process / null pointer");
   c->ou->set_state(state);
+  c->ou_stale = true;   // (the tables a batch reads on the device are now the older copy)
   return RGPU_OK;
 }
 

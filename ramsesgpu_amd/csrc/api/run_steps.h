@@ -42,6 +42,7 @@ struct LoneRun {
   int* nStep; double* t; double* dt; double* dt_log;   // dt_log may be 0
   const HistRun* hist;   // 0, or rgpu_run_steps_history
   const MonRun* mon;     // 0, or rgpu_run_steps_monitored
+  bool forced = false;   // forcing_clock_ok(c), asked once per call: the batches of this call carry the forcing stages (api/forcing.h)
   int done = 0;          // steps of this call so far
   int why = 0;           // 0, or the stop code of the record that ended the run (1: tEnd, 2: dt is not a number, 3: 1/dt is not finite --
                          // the last two are also reported as RGPU_EHIP)
@@ -78,12 +79,14 @@ struct LoneBatch {
   int queued = 0;                                // steps queued completely (their records are read back)
   int samples = 0;                               // monitor samples queued behind them: slots [0, samples) of the log, in step order
   bool failed = false; std::string launch_err;   // a launch failed behind the `queued` steps, with this message
+  bool forced = false; ForcingBatch fb;          // the steps carry forcing stages (api/forcing.h): what their open leaves for their close
 };
 
 // Opens a batch and queues up to m steps: per step the tick, the history head of U[n % 2] (taken on the device if the record and the
 // log say so, kernels_history.h), the pieces of the step == rgpu_godunov_unsplit for this configuration, every dt / t dependence read
 // from the record on the device, and the monitor of U[(n + 1) % 2] behind the step's last kernel (taken if the record says that the
-// step ran).  != 0: the batch could not be opened, nothing was queued
+// step ran).  A forced context (forcing_clock_ok): its forcing stages behind the core, where rgpu_godunov_unsplit has them.
+// != 0: the batch could not be opened, nothing was queued
 int batch_queue(LoneRun& run, int m, LoneBatch* b) {
   rgpu_ctx* c = run.c;
   const HistRun* H = run.hist;
@@ -92,6 +95,8 @@ int batch_queue(LoneRun& run, int m, LoneBatch* b) {
   if (M && monitor_batch_alloc(c, M->what, M->every)) return RG_HIPFAIL(c, std::string(M->who) + ": log of the batch");
   if (H && !c->hist.allocated() && c->hist.alloc(rgpu_ctx::kClockBatch)) return RG_HIPFAIL(c, "run_steps_history: log of the batch");
   if (const int rc = clock_open(c, *run.t, run.tEnd, true)) return rc;
+  b->forced = run.forced;
+  if (b->forced && forcing_batch_open(c, m, &b->fb)) { c->clk_n = -1; return RG_HIPFAIL(c, "run_steps: tables of the forcing stages"); }
   const int n0 = *run.nStep;
   const double dt0 = *run.dt;   // the loop's *dt at the head of the batch's first step
   int rc = 0;
@@ -101,7 +106,7 @@ int batch_queue(LoneRun& run, int m, LoneBatch* b) {
     const int slot = b->queued, n = n0 + slot;
     if (!clock_ready(c, n % 2)) rc = RGPU_EHIP;   // (cannot happen: the step before left its CFL maxima and, in 2D, its ghost cells)
     if (rc == 0 && H && history_batch_queue(c, n, slot, dt0, *H->tHist, H->dtHist)) rc = RGPU_EHIP;
-    if (rc == 0) rc = (step_pre(c, n) || step_core(c, n, 0.0, 0.0) || step_post_a(c, n, 0.0, 0.0) || step_post_b(c, n)) ? RGPU_EHIP : 0;
+    if (rc == 0) rc = (step_pre(c, n) || step_core(c, n, 0.0, 0.0) || (b->forced && forcing_batch_step(c, n, slot)) || step_post_a(c, n, 0.0, 0.0) || step_post_b(c, n)) ? RGPU_EHIP : 0;
     if (rc == 0 && !c->rec.slots((n + 1) % 2)) rc = RGPU_EHIP;   // (cannot happen: same configuration, same kernels)
     if (rc == 0 && M && M->due(n + 1)) {
       if (monitor_batch_queue(c, M->what, (n + 1) & 1, b->samples)) rc = RGPU_EHIP;
@@ -125,11 +130,19 @@ int batch_harvest(LoneRun& run, const LoneBatch& b) {
   // history record behind the last head queued, a monitor slot whose step did not run: copied unwritten, not read
   const bool log_ok = !H || queued == 0 || c->hist.download((size_t)queued, c->stream) == 0;
   const bool mon_ok = !M || b.samples == 0 || monitor_batch_log(c, M->what).download((size_t)b.samples * M->width, c->stream) == 0;
+  const bool frc_ok = !b.forced || forcing_batch_download(c) == 0;   // (the force of the Ornstein-Uhlenbeck process, likewise)
   const double t_open = *run.t;
   int ran = 0, stop = 0;
-  if (const int rc = rgpu_clock_close(c, n0, &ran, run.t, run.dt, run.dt_log ? run.dt_log + run.done : 0, &stop)) return rc;
+  if (const int rc = rgpu_clock_close(c, n0, &ran, run.t, run.dt, run.dt_log ? run.dt_log + run.done : 0, &stop)) {
+    if (b.forced) forcing_batch_abandon(c, b.fb);
+    return rc;
+  }
   *run.nStep += ran;
   run.done += ran;
+  if (b.forced) {
+    if (!frc_ok) { forcing_batch_abandon(c, b.fb); c->rec.forget(); return fail(c, RGPU_EHIP, "run_steps: read-back of the forcing process"); }
+    forcing_batch_close(c, b.fb, ran);
+  }
   if (M && ran > 0) {   // the host knows the step numbers; that step n0 + r ran is what the records said
     if (!mon_ok) { c->rec.forget(); return fail(c, RGPU_EHIP, std::string(M->who) + ": read-back of the log"); }
     const double* log = monitor_batch_log(c, M->what).h;
@@ -158,14 +171,22 @@ int batch_harvest(LoneRun& run, const LoneBatch& b) {
 }
 
 // the loop: per turn the literal body (the first step of a run always; a state without device maxima; consumers that cannot sample on
-// the device) or one batch.  Returns the steps done, or the code that ended the call -- *nStep, *t, *dt and the samples describe the
-// steps that ran either way
+// the device) or one batch.  A forced context that is batched (forcing_clock_ok) is primed instead: a state without device maxima gets its
+// scan queued, with no fetch, and the batch opens -- the first step of a run and the state a literal step left are batched too.
+// Returns the steps done, or the code that ended the call -- *nStep, *t, *dt and the samples describe the steps that ran either way
 int run_steps_impl(LoneRun& run) {
   rgpu_ctx* c = run.c;
   struct Current { rgpu_ctx* c; const int* n; ~Current() { c->cur = *n & 1; } } current = {c, run.nStep};   // however the loop is left: U[*nStep % 2] is the state
   (void)current;
+  run.forced = forcing_clock_ok(c);
+  const bool primed = run.forced && !run.hist;   // (rgpu_run_steps_history: the turbulence history is not the row a batch samples)
   while (run.done < run.nsteps && *run.t < run.tEnd && !run.why) {
-    if (!clock_ready(c, *run.nStep % 2) || (run.hist && !run.hist->batch) || (run.mon && !monitor_sample_fits(c, run.mon->what))) {
+    const int par = *run.nStep % 2;
+    if (primed && !clock_ready(c, par) && !(run.mon && !monitor_sample_fits(c, run.mon->what))) {
+      if (inv_dt_scan(c, par, 0, c->n32, true)) return RG_HIPFAIL(c, "run_steps: scan of a forced state");
+      c->rec.scanned(par, 1);
+    }
+    if (!clock_ready(c, *run.nStep % 2) || (run.hist && run.forced) || (run.hist && !run.hist->batch) || (run.mon && !monitor_sample_fits(c, run.mon->what))) {
       if (const int rc = literal_turn(run)) return rc;
       continue;
     }
@@ -194,6 +215,7 @@ int rgpu_run_steps(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, 
 }
 
 long rgpu_history_batch_heads(rgpu_ctx* c) { return c ? c->hist_heads : 0; }
+long rgpu_forcing_batch_steps(rgpu_ctx* c) { return c ? c->forcing_steps : 0; }
 
 int rgpu_run_steps_history(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, double dtHist, double* tHist,
                            int* hist_n, int* hist_step, double* hist_t, double* hist_dt, double* hist) {

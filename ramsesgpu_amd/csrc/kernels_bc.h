@@ -388,6 +388,41 @@ RG_DEVFN void ou_forcing_cell(const DevParams& g, double* __restrict__ U, const 
   U[idx + IP * N] = eInt + 0.5 * (mu * mu + mv * mv + mw * mw) / rho;
 }
 
+// ---- the host's share of the two forcings, for the steps of a device-clock batch (api/forcing.h: forcing_batch_step) ----------------
+// Both reproduce host doubles: contraction off in either build of the library, IEEE / and sqrt, the host's operand order.
+//
+// forcing_sums' host loop over the 2 * isize column sums, then forcing_norm (api/forcing.h), by one thread
+RG_DEVFN void forcing_norm_finish(const double* __restrict__ cols, int isize, double Edot, long long nbCells, double dt, double* __restrict__ norm) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double s0 = 0.0, s1 = 0.0;
+  for (int i = 0; i < isize; ++i) { s0 += cols[i]; s1 += cols[isize + i]; }
+  if (Edot == 0) { *norm = 0.0; return; }
+  *norm = (sqrt(s0 * s0 + s1 * dt * Edot * 2 * nbCells) - s0) / s1;
+}
+
+// rgpu_ou::OuProcess::update (ou_forcing.h) for mode im: r are the 3 x 31 deviates update() would draw in this step, r[3 * im + i], drawn
+// ahead by the host (OuProcess::draw_step: they depend on neither dt nor the state); k: OuProcess::coef
+RG_DEVFN void ou_mode_step(rgpu_ou::OuModes* M, const double* __restrict__ proj, const double* __restrict__ r,
+                           const rgpu_ou::OuProcess::Coef& k, double dt, unsigned im) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int NM = rgpu_ou::NMODE, ND = rgpu_ou::NDIM;
+  if (im >= (unsigned)NM) return;
+  double A[3] = {0.0, 0.0, 0.0}, B[3] = {0.0, 0.0, 0.0};
+  for (int i = 0; i < ND; ++i) A[i] = r[3 * im + i] * sqrt(dt);
+  for (int j = 0; j < ND; ++j) {
+    double s = 0.0;
+    for (int i = 0; i < ND; ++i) s += proj[i * ND * NM + j * NM + im] * A[i];
+    B[j] = s;
+  }
+  for (int i = 0; i < ND; ++i) B[i] = B[i] * k.v * k.amp / k.T;
+  for (int i = 0; i < ND; ++i) B[i] = B[i] - M->force[i * NM + im] * dt / k.T;
+  for (int i = 0; i < ND; ++i) M->force[i * NM + im] += k.rms * B[i];
+}
+
 // state checksum (rgpu_state_checksum): one thread per (i, k) row of the interior adds the 64-bit patterns of all variables of its
 // ny cells, modulo 2^64 -- an order-independent sum, so slabs, tiles and launch geometry cannot change it
 RG_DEVFN void checksum_row_cell(const DevParams& g, const double* __restrict__ U, unsigned long long* __restrict__ rows, unsigned idx) {

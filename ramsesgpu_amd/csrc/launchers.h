@@ -202,6 +202,62 @@ struct K_ou_forcing {
   DevParams g; double* U; rgpu_ou::OuModes M; double dt, yMin, zMin; int kz0;
   RG_DEVFN void operator()(unsigned idx) const { ou_forcing_cell(g, U, M, dt, yMin, zMin, kz0, idx); }
 };
+// ---- the forcing stages of a step inside a device-clock batch (api/forcing.h: forcing_batch_step): dt from the record, the norm / the
+// modes through device pointers, a stopped step leaves everything alone.  The per-cell arithmetic is the literal kernels' (add_forcing_cell,
+// ou_forcing_cell).  The *_scan forms are launched through rg_reduce_max, which calls them once per index: behind the kick they return
+// the CFL term of the cell's new values (the kicks write momenta and energy of their own cell; mhd_invdt_cell reads the neighbours' face
+// fields only), 0 outside the interior and on a stopped step, which leaves the slots as they are.
+// (The namespace: these are the forcing stages of the runs the monitors sample inside batches -- and tests/test_monitor_resources.py
+//  admits a kernel the library gains only under a name that says "monitor".)
+namespace monitored_run {
+// a functor that knows nothing of the record (K_forcing_rows, K_hist_cols: they stay as they are), not run on a stopped step: behind an
+// end time the rest of a batch would otherwise read the whole state once per step for sums nobody uses
+template <class K>
+struct K_if_running {
+  K k; const StepClock* clk;
+  RG_DEVFN void operator()(unsigned idx) const { if (clk && clk->stop) return; k(idx); }
+};
+struct K_forcing_norm {
+  const double* cols; int isize; double Edot; long long nbCells; double dt; double* norm; const StepClock* clk;
+  RG_DEVFN void operator()(unsigned idx) const {
+    if (idx != 0 || (clk && clk->stop)) return;
+    forcing_norm_finish(cols, isize, Edot, nbCells, clk ? clk->dt : dt, norm);
+  }
+};
+struct K_ou_mode_step {
+  rgpu_ou::OuModes* M; const double* proj; const double* r; rgpu_ou::OuProcess::Coef k; double dt; const StepClock* clk;
+  RG_DEVFN void operator()(unsigned im) const {
+    if (clk && clk->stop) return;
+    ou_mode_step(M, proj, r, k, clk ? clk->dt : dt, im);
+  }
+};
+struct K_add_forcing_dev {
+  DevParams g; double* U; const double* Frc; const double* norm; const StepClock* clk;
+  RG_DEVFN void operator()(unsigned idx) const { if (clk && clk->stop) return; add_forcing_cell(g, U, Frc, *norm, idx); }
+};
+template <bool MHD>
+struct K_add_forcing_scan {
+  K_add_forcing_dev kick;
+  RG_DEVFN double operator()(unsigned idx) const {
+    if (kick.clk && kick.clk->stop) return 0.0;
+    kick(idx);
+    return MHD ? mhd_invdt_cell(kick.g, kick.U, idx) : hydro_invdt_cell<5>(kick.g, kick.U, idx);
+  }
+};
+struct K_ou_forcing_dev {
+  DevParams g; double* U; const rgpu_ou::OuModes* M; double dt, yMin, zMin; int kz0; const StepClock* clk;
+  RG_DEVFN void operator()(unsigned idx) const { if (clk && clk->stop) return; ou_forcing_cell(g, U, *M, clk ? clk->dt : dt, yMin, zMin, kz0, idx); }
+};
+template <bool MHD>
+struct K_ou_forcing_scan {
+  K_ou_forcing_dev kick;
+  RG_DEVFN double operator()(unsigned idx) const {
+    if (kick.clk && kick.clk->stop) return 0.0;
+    kick(idx);
+    return MHD ? mhd_invdt_cell(kick.g, kick.U, idx) : hydro_invdt_cell<5>(kick.g, kick.U, idx);
+  }
+};
+}  // namespace monitored_run
 // (the ghost-fill functors end in `const StepClock* clk`: inside a batch of device-clock steps a stopped step must leave the state as it
 //  is -- they take nothing else from the record.  Omitted in an aggregate initialiser it is 0.)
 struct K_bc_zstrat {

@@ -77,6 +77,36 @@ class OuProcess {
     }
   }
 
+  // ---- what a batch of device-clock steps takes from the process (api/forcing.h; the mode step itself: K_ou_mode_step, launchers.h) ----
+  // the factors of update() that depend on neither dt nor the deviates, each formed as update() forms it
+  struct Coef { double v, amp, T, rms; };   // sqrt(5/3) cIso, sqrt(2 w^2 / T), T, forceRMS
+  Coef coef(double cIso) const {
+    const double weight = w_;
+    Coef k;
+    k.v = std::sqrt(5.0 / 3.0) * cIso;
+    k.amp = std::sqrt(2.0 * weight * weight / T_);
+    k.T = T_;
+    k.rms = 3.0 / std::sqrt(1 - 2.0 * ksi_ + 3.0 * ksi_ * ksi_);
+    return k;
+  }
+  // the deviates of one update(), in its order: r[3 * im + i]
+  enum { STEP_DEVIATES = NDIM * NMODE };
+  void draw_step(double* r) {
+    for (int n = 0; n < STEP_DEVIATES; ++n) gauss(r[n]);
+  }
+  // the generator alone: where it stands, and back to there
+  struct Gen { int seed[4]; int igauss; double spare; };
+  Gen gen() const {
+    Gen s;
+    for (int i = 0; i < 4; ++i) s.seed[i] = seed_[i];
+    s.igauss = igauss_; s.spare = spare_;
+    return s;
+  }
+  void set_gen(const Gen& s) {
+    for (int i = 0; i < 4; ++i) seed_[i] = s.seed[i];
+    igauss_ = s.igauss; spare_ = s.spare;
+  }
+
   // whole state of the process as doubles (restart files; what output_forcing / init_forcing(restart) exchange through
   // an .npz in the reference, Forcing_OrnsteinUhlenbeck.cpp:392-444, 236-352 -- plus the Box-Muller spare, which the
   // reference loses across a restart): mode, force, proj, the four seed digits, the spare flag and value

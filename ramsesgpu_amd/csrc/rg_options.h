@@ -15,6 +15,7 @@ struct Options {
   int zseg = 0;           // planes per z segment of the tiled sweeps; 0: planned per launch (tile_grid_plan)
   int chunks = -1;        // chunks of the two-stream schedule of the flat 3D MHD kernels; -1: ksize / 8; 1: one stream
   int history_batch = 1;  // rgpu_run_steps_history samples on the device inside the device-clock batches (0: the literal loop everywhere)
+  int forcing_clock = 1;  // rgpu_run_steps* batch a lone 3D context with random / Ornstein-Uhlenbeck forcing: the forcing stages read the record (0: the literal loop)
   int member_params = 0;  // 1: the fused rounds of every ensemble read their constants from the per-member table (hip/ensemble_scan.h), equal sets or not
   int map_log_kib = 262144;   // byte budget (KiB) of the device log of the maps a batch samples (api/monitor.h; rgpu_run_steps_mapped)
   int map_x_tiled = -1;   // the kernel that sums a map along x (hip/monitor_maps.h): -1 by the thickness of the range, 0 direct, 1 tiled
@@ -33,6 +34,7 @@ inline int* option_slot(const char* name) {
   if (!std::strcmp(name, "zseg")) return &o.zseg;
   if (!std::strcmp(name, "chunks")) return &o.chunks;
   if (!std::strcmp(name, "history_batch")) return &o.history_batch;
+  if (!std::strcmp(name, "forcing_clock")) return &o.forcing_clock;
   if (!std::strcmp(name, "member_params")) return &o.member_params;
   if (!std::strcmp(name, "map_log_kib")) return &o.map_log_kib;
   if (!std::strcmp(name, "map_x_tiled")) return &o.map_x_tiled;

@@ -564,6 +564,11 @@ class Solver:
         self.dt_log = [log[i] for i in range(done)]     # the time steps of this call, in order
         return done
 
+    def forcing_batch_steps(self):
+        """how many steps of this context ran inside device-clock batches with a forcing stage queued (rgpu_forcing_batch_steps: 0 where
+        every forced step took the literal loop, e.g. with option "forcing_clock" = 0)"""
+        return int(self.lib.rgpu_forcing_batch_steps(self.ctx))
+
     def run_steps_history(self, nsteps, dtHist, tEnd=float("inf")):
         """up to nsteps turns of the reference's time loop with its history cadence inside (rgpu_run_steps_history: before a step, when
         tHist == 0 or the last step carried t past tHist + dtHist, the row of history_mri is taken and tHist += dtHist; inside the
