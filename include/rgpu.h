@@ -892,6 +892,73 @@ int rgpu_run_steps_spectra(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, dou
                            double* spectra /* [cap][sum of 2 S] */);
 long rgpu_spectrum_batch_samples(rgpu_ctx* c);
 
+/* ---- Helmholtz spectra: solenoidal and compressive power of a vector field per shell, taken on the device ---------------------------
+ * The sixth shape of the family: how the power of a vector field splits, shell by shell, into the part transverse to the wave vector
+ * (solenoidal) and the part along it (compressive) -- the diagnostic of a driven run (what its forcing really injects: DESIGN 3.4.8),
+ * the sound-wave content of w = m / sqrt(rho), the distance of the cell-centred B from the divergence-free face field.
+ * rgpu_state_spectra cannot give it: it packs two real channels into one complex transform, so the components of a vector never meet
+ * at the same mode.
+ * Context: that of the spectrum monitors above, word for word -- a lone single-domain 3D context, extents powers of two in 4 .. 1024,
+ * the box taken as periodic, the interior cells of U[parity] as the array stands, the plain lab-frame transform in a shearing box.
+ * A spec: { field; wx, wy, wz }.  `field` indexes RGPU_HELM_NAMES: m, v, w, b are the channel triples 1-3, 4-6, 7-9 and 10-12 of
+ * RGPU_SPECTRUM_NAMES, formed by the same code (csrc/kernels_monitor_helm.h picks them, it restates nothing).  The weights are
+ * integers 1 .. RGPU_SPECTRUM_MAX_WEIGHT; a zero weight is refused, because here the weights also give the wave vector its direction
+ * and a dropped axis has none.
+ * With u^_a(k), a = x, y, z, the transforms of the three components as defined above and k_a the SIGNED folded wave number
+ * (-n_a / 2 .. n_a / 2 - 1: the Nyquist index counts as -n_a / 2), kappa_a = w_a k_a (an exact double), q = kappa_x^2 + kappa_y^2 +
+ * kappa_z^2 is the integer of the spectrum monitors, the shell of q follows from the same integer rule, and a spec has the same S.
+ * Per mode, without contraction and in this order (helm_mode, the one definition every kernel uses):
+ *   d = (kappa_x u^_x + kappa_y u^_y) + kappa_z u^_z                 real and imaginary part separately
+ *   c = kappa x u^: c_x = kappa_y u^_z - kappa_z u^_y, c_y = kappa_z u^_x - kappa_x u^_z, c_z = kappa_x u^_y - kappa_y u^_x
+ *   q > 0:  L = (d.re^2 + d.im^2) / q,  T = ((|c_x|^2 + |c_y|^2) + |c_z|^2) / q      the division is the library's own (rg_div)
+ *   q = 0:  L = +0.0,  T = (|u^_x|^2 + |u^_y|^2) + |u^_z|^2                          the mean flow counts as solenoidal, in shell 0
+ * Both parts are computed directly, never one as the difference of the total and the other: a nearly pure field does not lose its
+ * small part to cancellation.  The output of a spec is 3 S doubles:
+ *   Psol[s] = sum of T over the modes of shell s,  Pcomp[s] = sum of L,  M[s] = the number of modes, as a double (an exact integer).
+ * Identities: sum_s (Psol[s] + Pcomp[s]) = (1 / N) sum_x |u(x)|^2 to rounding (|kappa x u^|^2 + |kappa . u^|^2 = q |u^|^2, Parseval);
+ * Psol[s] + Pcomp[s] agrees with P[s] of rgpu_state_spectra for the same three channels and weights within the bound below (twice
+ * it: each side has its own rounding); M equals that call's M word for word.
+ * How it is computed (csrc/hip/monitor_helm.h): per spec three transforms, one per component with imaginary part zero,
+ * into three arrays in the flux array.  The x and y passes are the spectrum monitor's kernels as they are; a z pass writes the first
+ * two arrays back; the binning pass transforms the third in LDS, reads the other two at the same mode, replaces each element of its
+ * tile by (T, L) and then bins with the owners, the column and the |kz| order of the spectrum monitor; a fold stores.
+ * Reproducibility: as for the spectrum monitors -- within one library the same doubles bit for bit on every call, wherever in a batch
+ * the sample is taken, whatever other specs share the call, and for every value of option "spectrum_tile_y"; no floating-point
+ * atomics, no zeroing pass; M the same in both libraries, word for word.  For each of Psol and Pcomp, against another FFT:
+ * |dP_c[s]| <= e (P_c[s] + 2 sqrt(P_c[s] Ptot)) + e^2 Ptot with Ptot = sum_s (Psol + Pcomp) -- the bound of the spectra carries over
+ * because both projections are contractions of u^ (tests: e = 1e-12; measured: DESIGN 3.4.8).
+ *
+ *   rgpu_helm_shells            S of *spec on this context; 0 for a context or a spec that is refused, for its scratch included.
+ *   rgpu_state_helm_spectra     nspec outputs of U[parity], one after another in `out` (spec m at the sum of 3 S of the specs before it:
+ *                               Psol[0 .. S), Pcomp[0 .. S), M[0 .. S)).  Reads the state only.  Synchronises.
+ *   rgpu_run_steps_helm_spectra rgpu_run_steps_spectra word for word with W = the sum of 3 S over the specs: the same states, dt
+ *                               sequence and return value as rgpu_run_steps_log, a sample after each step that brings *nStep to a
+ *                               multiple of `every`, each what rgpu_state_helm_spectra gives on that state, bit for bit; inside the
+ *                               device-clock batches the kernels of a sample are queued behind the qualifying step, gated by its clock
+ *                               record, and the log (RGPU_CLOCK_BATCH / every + 1 slots, a buffer of its own, not part of
+ *                               rgpu_device_bytes) is copied back once per batch; everywhere else the literal loop.  The table of
+ *                               twiddle factors is the spectrum monitors'.
+ *   rgpu_helm_batch_samples     how many samples this context has queued on the device inside its batches so far.  These calls leave
+ *                               the other monitors' counters alone, and the other monitors leave this one alone.
+ *   Errors (nothing has run, *mon_n == 0): those of the spectrum monitors -- RGPU_EUNSUPPORTED for a 2D context and for an extent that
+ *                               is not a power of two in 4 .. 1024; RGPU_EINVAL for a slab context, a NULL pointer, nsteps < 0,
+ *                               every < 1, nspec outside 1 .. RGPU_HELM_MAX, more than RGPU_SPECTRUM_MAX_SHELLS shells, a flux array too
+ *                               small for the three transforms and the partial sums of one workgroup (where it is too small for
+ *                               those of all workgroups of the binning pass, fewer run: the count follows from the box, the spec
+ *                               and the flux array of the context alone, and is part of the fixed summation order) -- and RGPU_EINVAL for `field` outside
+ *                               0 .. RGPU_HELM_NF - 1, a zero weight ("zero" in the message) or a weight outside
+ *                               1 .. RGPU_SPECTRUM_MAX_WEIGHT (the message names the spec, "spectrum 1: ..."). */
+#define RGPU_HELM_NF 4
+#define RGPU_HELM_NAMES "m v w b"   /* the RGPU_HELM_NF vector fields, in order */
+#define RGPU_HELM_MAX 4             /* specs per call */
+typedef struct { int field; int wx, wy, wz; } rgpu_helm_spec;
+int rgpu_helm_shells(rgpu_ctx* c, const rgpu_helm_spec* spec);
+int rgpu_state_helm_spectra(rgpu_ctx* c, int parity, int nspec, const rgpu_helm_spec* specs, double* out);
+int rgpu_run_steps_helm_spectra(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log,
+                                int every, int nspec, const rgpu_helm_spec* specs, int* mon_n, int* mon_step /* [cap] */, double* mon_t /* [cap] */,
+                                double* spectra /* [cap][sum of 3 S] */);
+long rgpu_helm_batch_samples(rgpu_ctx* c);
+
 /* Self-test of the device arithmetic the parity contract rests on: for n operand pairs computes on the device
  *   quot[i]  = rg_div(num[i], rg_recip(den[i]))   the shared-reciprocal division of csrc/hip/rg_backend.h
  *   quot2[i] = num[i] / den[i]                    the compiler's IEEE division

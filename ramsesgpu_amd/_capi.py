@@ -28,6 +28,11 @@ SPECTRUM_NQ = len(SPECTRUM_NAMES)
 SPECTRUM_MAX = 4
 SPECTRUM_MAX_SHELLS = 4096
 SPECTRUM_MAX_WEIGHT = 64
+# the vector fields of a Helmholtz spectrum (rgpu_state_helm_spectra, rgpu_run_steps_helm_spectra): RGPU_HELM_NF = 4, the channel
+# triples 1-3, 4-6, 7-9, 10-12 of SPECTRUM_NAMES
+HELM_NAMES = ("m", "v", "w", "b")
+HELM_NF = len(HELM_NAMES)
+HELM_MAX = 4
 T_NAMES = ["boundaries", "prim", "elec", "trace", "flux", "emf", "update", "shear", "dt", "dissipative", "sweep"]
 
 
@@ -104,6 +109,11 @@ class RgpuPdfSpec(C.Structure):
 class RgpuSpectrumSpec(C.Structure):
     """rgpu_spectrum_spec: the bit mask of the channels and the integer weights of the shell rule"""
     _fields_ = [("channels", C.c_uint), ("wx", C.c_int), ("wy", C.c_int), ("wz", C.c_int)]
+
+
+class RgpuHelmSpec(C.Structure):
+    """rgpu_helm_spec: the vector field (an index into HELM_NAMES) and the integer weights, none of them zero"""
+    _fields_ = [("field", C.c_int), ("wx", C.c_int), ("wy", C.c_int), ("wz", C.c_int)]
 
 
 def declare_host_api(lib):
@@ -298,6 +308,16 @@ def declare_device_api(lib):
                                                C.c_int, C.POINTER(RgpuSpectrumSpec), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]
         lib.rgpu_spectrum_batch_samples.restype = C.c_long
         lib.rgpu_spectrum_batch_samples.argtypes = [ctx]
+    if hasattr(lib, "rgpu_state_helm_spectra"):   # (absent from an older build of the library)
+        lib.rgpu_helm_shells.restype = C.c_int
+        lib.rgpu_helm_shells.argtypes = [ctx, C.POINTER(RgpuHelmSpec)]
+        lib.rgpu_state_helm_spectra.restype = C.c_int
+        lib.rgpu_state_helm_spectra.argtypes = [ctx, C.c_int, C.c_int, C.POINTER(RgpuHelmSpec), c_double_p]
+        lib.rgpu_run_steps_helm_spectra.restype = C.c_int
+        lib.rgpu_run_steps_helm_spectra.argtypes = [ctx, C.c_int, C.c_double, C.POINTER(C.c_int), c_double_p, c_double_p, c_double_p, C.c_int,
+                                                    C.c_int, C.POINTER(RgpuHelmSpec), C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p, c_double_p]
+        lib.rgpu_helm_batch_samples.restype = C.c_long
+        lib.rgpu_helm_batch_samples.argtypes = [ctx]
     return lib
 
 
@@ -352,4 +372,5 @@ DECLARED_SYMBOLS = [
     "rgpu_map_doubles", "rgpu_state_maps", "rgpu_run_steps_mapped", "rgpu_map_batch_samples",
     "rgpu_pdf_words", "rgpu_state_pdfs", "rgpu_run_steps_pdfs", "rgpu_pdf_batch_samples",
     "rgpu_spectrum_shells", "rgpu_state_spectra", "rgpu_run_steps_spectra", "rgpu_spectrum_batch_samples",
+    "rgpu_helm_shells", "rgpu_state_helm_spectra", "rgpu_run_steps_helm_spectra", "rgpu_helm_batch_samples",
 ]

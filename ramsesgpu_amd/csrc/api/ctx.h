@@ -121,6 +121,11 @@ struct rgpu_ctx {
   DeviceMirror<double> mons, montw;
   size_t mons_doubles = 0;
   long mons_samples = 0;        // spectrum samples queued on the device inside batches so far (rgpu_spectrum_batch_samples)
+  // the Helmholtz spectra (kernels_monitor_helm.h; rgpu_state_helm_spectra, rgpu_run_steps_helm_spectra): a buffer of their own on the
+  // same terms, monv_doubles doubles; the twiddle factors are montw
+  DeviceMirror<double> monv;
+  size_t monv_doubles = 0;
+  long monv_samples = 0;        // Helmholtz samples queued on the device inside batches so far (rgpu_helm_batch_samples)
   // the forcing stages inside a batch (api/forcing.h: forcing_batch_step; option "forcing_clock"), allocated by the first batch that needs
   // them.  frc_norm: the norm of the random forcing, formed and read on the device.  ou_tab: the process as the kernels see it -- mode,
   // force (an OuModes) and proj, kOuTab doubles -- uploaded from c->ou when ou_stale says that the host's copy is the newer one (creation,

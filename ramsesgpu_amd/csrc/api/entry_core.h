@@ -319,6 +319,8 @@ int rgpu_state_pdfs(rgpu_ctx* c, int parity, int npdfs, const rgpu_pdf_spec* spe
 size_t rgpu_pdf_words(const rgpu_pdf_spec* spec) { return spec && pdf_spec_error(*spec).empty() ? pdf_spec_words(*spec) : 0; }
 int rgpu_state_spectra(rgpu_ctx* c, int parity, int nspec, const rgpu_spectrum_spec* specs, double* out) { return state_spectra(c, parity, nspec, specs, out); }
 int rgpu_spectrum_shells(rgpu_ctx* c, const rgpu_spectrum_spec* spec) { return spectrum_shells(c, spec); }
+int rgpu_state_helm_spectra(rgpu_ctx* c, int parity, int nspec, const rgpu_helm_spec* specs, double* out) { return state_helm_spectra(c, parity, nspec, specs, out); }
+int rgpu_helm_shells(rgpu_ctx* c, const rgpu_helm_spec* spec) { return helm_shells(c, spec); }
 
 double rgpu_compute_dt(rgpu_ctx* c, int useU) {
   double v = 0;

@@ -2,7 +2,8 @@
 // rgpu_state_monitor (2D), rgpu_state_monitor3d and a sample queued inside a device-clock batch (rgpu_run_steps_monitored); the same for
 // the plane monitor (kernels_monitor_planes.h: rgpu_state_monitor_planes, rgpu_run_steps_monitored_planes) and for the map monitor
 // (kernels_monitor_maps.h: rgpu_state_maps, rgpu_run_steps_mapped), for the PDF monitor (kernels_monitor_pdf.h: rgpu_state_pdfs,
-// rgpu_run_steps_pdfs) and for the spectrum monitor (kernels_monitor_spectrum.h: rgpu_state_spectra, rgpu_run_steps_spectra).  See api/ctx.h.
+// rgpu_run_steps_pdfs), for the spectrum monitor (kernels_monitor_spectrum.h: rgpu_state_spectra, rgpu_run_steps_spectra) and for the
+// Helmholtz spectra (kernels_monitor_helm.h: rgpu_state_helm_spectra, rgpu_run_steps_helm_spectra).  See api/ctx.h.
 #pragma once
 namespace {
 // One route for either dimension, a 2D state being a volume of one plane.  Everything on the device, the sum over the planes included,
@@ -367,30 +368,129 @@ int state_spectra(rgpu_ctx* c, int parity, int nspec, const rgpu_spectrum_spec* 
   return spectra_take(c, who, parity, S, out);
 }
 
-// ---- the samples of a batch: of the monitor, of the plane monitor, of the map monitor, of the PDF or of the spectrum monitor ---------
+// ---- the Helmholtz spectra (kernels_monitor_helm.h): the same consumer with a sixth sample, 3 S doubles per spec ----------------------
+static_assert(HELM_NF == RGPU_HELM_NF && HELM_MAX == RGPU_HELM_MAX, "include/rgpu.h states the fields and the limits of the Helmholtz spectra");
+// "" for a spec this context can take, else what is wrong with it (the box can be taken)
+std::string helm_spec_error(const rgpu_ctx* c, const rgpu_helm_spec& s) {
+  if (s.field < 0 || s.field >= RGPU_HELM_NF) return "field must be 0 .. " + std::to_string(RGPU_HELM_NF - 1);
+  const int w[3] = {s.wx, s.wy, s.wz};
+  for (int a = 0; a < 3; ++a) {
+    if (w[a] == 0) return std::string("w") + "xyz"[a] + " is zero (the weights give the wave vector its direction)";
+    if (w[a] < 0 || w[a] > RGPU_SPECTRUM_MAX_WEIGHT) return std::string("w") + "xyz"[a] + " must be 1 .. " + std::to_string(RGPU_SPECTRUM_MAX_WEIGHT);
+  }
+  const unsigned long long shells = spec_shell_count(spec_box(c->g), s.wx, s.wy, s.wz);
+  if (shells > (unsigned long long)RGPU_SPECTRUM_MAX_SHELLS) return std::to_string(shells) + " shells, more than " + std::to_string(RGPU_SPECTRUM_MAX_SHELLS);
+  return "";
+}
+// the shells of a spec on this context, 0 if the context or the spec is refused
+// the doubles of the flux array, the scratch of a sample
+size_t helm_scratch_capacity(const rgpu_ctx* c) { return c->F ? (size_t)c->g.fN * plan_for(c->p).f : 0; }
+int helm_shells(const rgpu_ctx* c, const rgpu_helm_spec* s) {
+  if (!c || !s || !c->U[0] || !c->g.three_d || c->p.slab_count > 1 || !spectrum_box_error(c).empty() || !helm_spec_error(c, *s).empty()) return 0;
+  const SpecBox b = spec_box(c->g);
+  const unsigned shells = (unsigned)spec_shell_count(b, s->wx, s->wy, s->wz);
+  return helm_bin_groups(b, shells, helm_scratch_capacity(c)) ? (int)shells : 0;   // (refused for its scratch: refused)
+}
+// the device buffer the samples are stored to: spectrum_log_reserve for a buffer of their own
+int helm_log_reserve(rgpu_ctx* c, size_t doubles) {
+  if (c->monv.allocated() && c->monv_doubles >= doubles) return 0;
+  c->monv.release();
+  c->monv_doubles = 0;
+  if (c->monv.alloc(doubles)) return -1;
+  c->monv_doubles = doubles;
+  return 0;
+}
+// what rgpu_state_helm_spectra and rgpu_run_steps_helm_spectra refuse alike, in the order of spectra_refusal; 0: the spectra can be
+// taken, and *S is what the kernels read
+int helm_refusal(rgpu_ctx* c, const std::string& who, int nspec, const rgpu_helm_spec* specs, HelmSet* S) {
+  if (!c->U[0]) return fail(c, RGPU_EINVAL, who + ": context without state");
+  if (!c->g.three_d) return fail(c, RGPU_EUNSUPPORTED, who + ": 3D contexts only");
+  const std::string box = spectrum_box_error(c);
+  if (!box.empty()) return fail(c, RGPU_EUNSUPPORTED, who + ": " + box);
+  if (c->p.slab_count > 1) return fail(c, RGPU_EINVAL, who + ": single-domain contexts only (a slab holds a part of the box)");
+  if (nspec < 1 || nspec > RGPU_HELM_MAX) return fail(c, RGPU_EINVAL, who + ": nspec must be 1 .. " + std::to_string(RGPU_HELM_MAX));
+  const SpecBox b = spec_box(c->g);
+  unsigned doubles = 0;
+  for (int m = 0; m < nspec; ++m) {
+    const std::string why = helm_spec_error(c, specs[m]);
+    if (!why.empty()) return fail(c, RGPU_EINVAL, who + ": spectrum " + std::to_string(m) + ": " + why);
+    HelmOne& o = S->s[m];
+    o.field = specs[m].field; o.wx = specs[m].wx; o.wy = specs[m].wy; o.wz = specs[m].wz;
+    o.shells = (int)spec_shell_count(b, o.wx, o.wy, o.wz);
+    o.base = doubles;
+    doubles += 3u * (unsigned)o.shells;
+    S->groups[m] = helm_bin_groups(b, (unsigned)o.shells, helm_scratch_capacity(c));
+    if (S->groups[m] == 0) return fail(c, RGPU_EINVAL, who + ": spectrum " + std::to_string(m) + ": no scratch for the three transforms and the partial sums");
+  }
+  S->n = nspec;
+  S->doubles = doubles;
+  if (spectrum_twiddles(c)) return RG_HIPFAIL(c, who + ": table of the twiddle factors");
+  return RGPU_OK;
+}
+// queues the Helmholtz spectra of U into dst[S.doubles] (device); clk as for spectra_queue.  The one place that knows whether the
+// backend has kernels of its own
+int helm_queue(rgpu_ctx* c, const double* U, const StepClock* clk, const HelmSet& S, double* dst) {
+#ifdef RGPU_TILED_MONITOR_HELM
+  return rgpu_tiled::launch_monitor_helm(c->stream, c->g, S, rgpu::options().spectrum_tile_y, U, c->montw.d, clk, c->F, dst);
+#else
+  const SpecBox b = spec_box(c->g);
+  const size_t cells = (size_t)b.nx * b.ny * b.nz;
+  const double N = (double)cells;
+  for (int m = 0; m < S.n; ++m) {
+    for (int a = 0; a < 3; ++a) {
+      double* Z = c->F + 2 * cells * (size_t)a;
+      K_mon_spectrum_x kx = {c->g, b, helm_first_channel(S.s[m].field) + a, -1, U, c->montw.d, Z, clk};
+      K_mon_spectrum_line ky = {b, 1, c->montw.d, Z, clk};
+      K_mon_spectrum_line kz = {b, 2, c->montw.d, Z, clk};
+      if (rg_launch<kBlock>(c->stream, (unsigned)(b.ny * b.nz), kx) || rg_launch<kBlock>(c->stream, (unsigned)(b.nx * b.nz), ky) || rg_launch<kBlock>(c->stream, (unsigned)(b.nx * b.ny), kz)) return -1;
+    }
+    K_mon_helm_bin kb = {b, S.s[m], 1.0 / (N * N), c->F, c->F + 2 * cells, c->F + 4 * cells, dst, clk};
+    if (rg_launch<kBlock>(c->stream, (unsigned)S.s[m].shells, kb)) return -1;
+  }
+  return 0;
+#endif
+}
+// one sample of U[parity] outside a batch, of a set that was not refused
+int helm_take(rgpu_ctx* c, const std::string& who, int parity, const HelmSet& S, double* out) {
+  if (helm_log_reserve(c, S.doubles)) return RG_HIPFAIL(c, who + ": device buffer of the spectra");
+  if (helm_queue(c, c->U[parity & 1], 0, S, c->monv.d) || rg_copy_d2h(out, c->monv.d, S.doubles * sizeof(double), c->stream) || rg_stream_sync(c->stream))
+    return RG_HIPFAIL(c, who);
+  return RGPU_OK;
+}
+int state_helm_spectra(rgpu_ctx* c, int parity, int nspec, const rgpu_helm_spec* specs, double* out) {
+  RG_CHECK_CTX(c);
+  const std::string who = "state_helm_spectra";
+  if (!out || !specs) return fail(c, RGPU_EINVAL, who + ": null pointer");
+  HelmSet S;
+  if (const int rc = helm_refusal(c, who, nspec, specs, &S)) return rc;
+  return helm_take(c, who, parity, S, out);
+}
+
+// ---- the samples of a batch: of the monitor, of the plane, map, PDF or spectrum monitor, or of the Helmholtz spectra ------------------
 // which sample a call takes (and, for maps and PDFs, of what).  Samples are 8-byte words, doubles or counts: the loop only copies them
-enum MonWhat { MON_MONITOR, MON_PLANES, MON_MAPS, MON_PDFS, MON_SPECTRA };
-struct MonSample { MonWhat what; int nmaps; const rgpu_map_spec* specs; const PdfSet* pdf; const SpecSet* spec; };
+enum MonWhat { MON_MONITOR, MON_PLANES, MON_MAPS, MON_PDFS, MON_SPECTRA, MON_HELM };
+struct MonSample { MonWhat what; int nmaps; const rgpu_map_spec* specs; const PdfSet* pdf; const SpecSet* spec; const HelmSet* helm; };
 size_t monitor_sample_doubles(const rgpu_ctx* c, const MonSample& S) {
+  if (S.what == MON_HELM) return (size_t)S.helm->doubles;
   if (S.what == MON_SPECTRA) return (size_t)S.spec->doubles;
   if (S.what == MON_PDFS) return (size_t)S.pdf->words;
   return S.what == MON_MAPS ? maps_sample_doubles(c, S.nmaps, S.specs) : S.what == MON_PLANES ? monp_sample_doubles(c->g) : (size_t)MON_NQ;
 }
 // whether the samples of this context can be taken inside its device-clock batches.  Maps need no scratch: one sample within the
-// budget.  PDFs and spectra: their scratch was checked with the specs
+// budget.  PDFs and both kinds of spectra: their scratch was checked with the specs
 bool monitor_sample_fits(rgpu_ctx* c, const MonSample& S) {
-  if (S.what == MON_PDFS || S.what == MON_SPECTRA) return true;
+  if (S.what == MON_PDFS || S.what == MON_SPECTRA || S.what == MON_HELM) return true;
   if (S.what == MON_MAPS) return c->g.three_d && monitor_sample_doubles(c, S) <= map_log_budget_doubles();
   return S.what == MON_PLANES ? monitor_planes_scratch_fits(c) : monitor_scratch_fits(c);
 }
-DeviceMirror<double>& monitor_batch_log(rgpu_ctx* c, const MonSample& S) { return S.what == MON_SPECTRA ? c->mons : S.what == MON_PDFS ? c->monh : S.what == MON_MAPS ? c->monm : S.what == MON_PLANES ? c->monp : c->mon; }
+DeviceMirror<double>& monitor_batch_log(rgpu_ctx* c, const MonSample& S) { return S.what == MON_HELM ? c->monv : S.what == MON_SPECTRA ? c->mons : S.what == MON_PDFS ? c->monh : S.what == MON_MAPS ? c->monm : S.what == MON_PLANES ? c->monp : c->mon; }
 // The slots of the log of a call that samples every `every` steps.  The monitor's: a slot per step of a batch.  The plane monitor's:
 // a slot per sample that can fall into one batch.  The maps': as many, or as the budget holds if that is fewer (at least one:
 // monitor_sample_fits)
 size_t monitor_batch_slots(const rgpu_ctx* c, const MonSample& S, int every) {
   if (S.what == MON_MONITOR) return (size_t)rgpu_ctx::kClockBatch;
   const size_t slots = (size_t)rgpu_ctx::kClockBatch / (size_t)every + 1;
-  if (S.what == MON_PLANES || S.what == MON_PDFS || S.what == MON_SPECTRA) return slots;   // (a PDF sample is at most 128 KiB, the spectra 256 KiB: no byte budget)
+  if (S.what == MON_PLANES || S.what == MON_PDFS || S.what == MON_SPECTRA || S.what == MON_HELM) return slots;   // (a PDF sample is at most 128 KiB, the spectra 256 KiB, the Helmholtz spectra 384 KiB: no byte budget)
   const size_t held = map_log_budget_doubles() / monitor_sample_doubles(c, S);
   return held < slots ? held : slots;
 }
@@ -407,6 +507,7 @@ int monitor_batch_alloc(rgpu_ctx* c, const MonSample& S, int every) {
   if (S.what == MON_MAPS) return map_log_reserve(c, n);
   if (S.what == MON_PDFS) return pdf_log_reserve(c, n);
   if (S.what == MON_SPECTRA) return spectrum_log_reserve(c, n);
+  if (S.what == MON_HELM) return helm_log_reserve(c, n);
   DeviceMirror<double>& log = monitor_batch_log(c, S);
   if (S.what == MON_PLANES && log.allocated() && c->monp_slots < slots) log.release();
   if (log.allocated()) return 0;
@@ -422,9 +523,9 @@ int monitor_batch_alloc(rgpu_ctx* c, const MonSample& S, int every) {
 int monitor_batch_queue(rgpu_ctx* c, const MonSample& S, int parity, int k) {
   double* dst = monitor_batch_log(c, S).d + (size_t)k * monitor_sample_doubles(c, S);
   const double* U = c->U[parity & 1];
-  const int rc = S.what == MON_SPECTRA ? spectra_queue(c, U, c->clk_cur, *S.spec, dst) : S.what == MON_PDFS ? pdfs_queue(c, U, c->clk_cur, *S.pdf, dst) : S.what == MON_MAPS ? maps_queue(c, U, c->clk_cur, S.nmaps, S.specs, dst)
+  const int rc = S.what == MON_HELM ? helm_queue(c, U, c->clk_cur, *S.helm, dst) : S.what == MON_SPECTRA ? spectra_queue(c, U, c->clk_cur, *S.spec, dst) : S.what == MON_PDFS ? pdfs_queue(c, U, c->clk_cur, *S.pdf, dst) : S.what == MON_MAPS ? maps_queue(c, U, c->clk_cur, S.nmaps, S.specs, dst)
                : S.what == MON_PLANES ? monitor_planes_queue(c, U, c->clk_cur, dst) : monitor_queue(c, U, c->clk_cur, dst);
-  if (rc == 0) ++(S.what == MON_SPECTRA ? c->mons_samples : S.what == MON_PDFS ? c->monh_samples : S.what == MON_MAPS ? c->monm_samples : S.what == MON_PLANES ? c->monp_samples : c->mon_samples);
+  if (rc == 0) ++(S.what == MON_HELM ? c->monv_samples : S.what == MON_SPECTRA ? c->mons_samples : S.what == MON_PDFS ? c->monh_samples : S.what == MON_MAPS ? c->monm_samples : S.what == MON_PLANES ? c->monp_samples : c->mon_samples);
   return rc;
 }
 

@@ -1,4 +1,4 @@
-// api/run_steps.h -- entry points: the time loop of a lone context (rgpu_run_steps, _log, _history, _monitored, _monitored_planes, _mapped, _pdfs, _spectra; every member-alone round
+// api/run_steps.h -- entry points: the time loop of a lone context (rgpu_run_steps, _log, _history, _monitored, _monitored_planes, _mapped, _pdfs, _spectra, _helm_spectra; every member-alone round
 // of an ensemble comes through here too).  One LoneRun per call; per turn either the reference's loop body (literal_turn) or a batch
 // of device-clock steps (api/entry_clock.h), queued by batch_queue and read back once by batch_harvest.  The two optional consumers
 // of a step -- the history row in front of it, the monitor sample behind it -- each write the caller's arrays in one place, put().
@@ -65,7 +65,8 @@ int literal_turn(LoneRun& run) {
   if (run.mon && run.mon->due(*run.nStep)) {
     const MonRun* M = run.mon;
     const int par = *run.nStep & 1;
-    if (const int rc = M->what.what == MON_SPECTRA ? spectra_take(c, M->who, par, *M->what.spec, M->slot())
+    if (const int rc = M->what.what == MON_HELM ? helm_take(c, M->who, par, *M->what.helm, M->slot())
+                     : M->what.what == MON_SPECTRA ? spectra_take(c, M->who, par, *M->what.spec, M->slot())
                      : M->what.what == MON_PDFS ? pdfs_take(c, M->who, par, *M->what.pdf, M->slot())
                      : M->what.what == MON_MAPS ? state_maps(c, par, M->what.nmaps, M->what.specs, M->slot())
                      : M->what.what == MON_PLANES ? state_monitor_planes(c, par, M->slot()) : state_monitor(c, c->g.three_d != 0, par, M->slot())) return rc;
@@ -311,6 +312,23 @@ int rgpu_run_steps_spectra(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, dou
   if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_spectra: every must be at least 1");
   const MonSample S = {MON_SPECTRA, 0, 0, 0, &set};
   const MonRun M = {every, S, (size_t)set.doubles, mon_n, mon_step, mon_t, spectra, "run_steps_spectra"};
+  LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
+  return run_steps_impl(run);
+}
+
+long rgpu_helm_batch_samples(rgpu_ctx* c) { return c ? c->monv_samples : 0; }
+
+int rgpu_run_steps_helm_spectra(rgpu_ctx* c, int nsteps, double tEnd, int* nStep, double* t, double* dt, double* dt_log, int every,
+                                int nspec, const rgpu_helm_spec* specs, int* mon_n, int* mon_step, double* mon_t, double* spectra) {
+  RG_CHECK_CTX(c);
+  if (mon_n) *mon_n = 0;
+  if (!nStep || !t || !dt || !specs || !mon_n || !mon_step || !mon_t || !spectra) return fail(c, RGPU_EINVAL, "run_steps_helm_spectra: null pointer");
+  HelmSet set;
+  if (const int rc = helm_refusal(c, "run_steps_helm_spectra", nspec, specs, &set)) return rc;
+  if (nsteps < 0) return fail(c, RGPU_EINVAL, "run_steps_helm_spectra: nsteps is negative");
+  if (every < 1) return fail(c, RGPU_EINVAL, "run_steps_helm_spectra: every must be at least 1");
+  const MonSample S = {MON_HELM, 0, 0, 0, 0, &set};
+  const MonRun M = {every, S, (size_t)set.doubles, mon_n, mon_step, mon_t, spectra, "run_steps_helm_spectra"};
   LoneRun run = {c, nsteps, tEnd, nStep, t, dt, dt_log, 0, &M};
   return run_steps_impl(run);
 }

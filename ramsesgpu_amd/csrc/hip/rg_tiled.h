@@ -28,3 +28,6 @@
 #include "monitor_spectrum.h"
 // the gfx950 kernels of the spectrum monitor exist (api/monitor.h: without this macro it runs the flat functors)
 #define RGPU_TILED_MONITOR_SPECTRUM 1
+#include "monitor_helm.h"
+// the gfx950 kernels of the Helmholtz spectra exist (api/monitor.h: without this macro they run the flat functors)
+#define RGPU_TILED_MONITOR_HELM 1

@@ -1071,6 +1071,88 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     if (!f) throw std::runtime_error("cannot write " + spectra_list);
     f << "# nStep totalTime spectrum spec file\n";
   }
+  // [helmholtz] enabled=yes every=N spectrum0="w 1 1 1" spectrum1="b 4 1 4" ... (up to spectrum3, numbered from 0 without a gap): the
+  // solenoidal and the compressive power per shell of a vector field (include/rgpu.h, "Helmholtz spectra") on the terms of [spectra].
+  // A spec is "<field> <wx> <wy> <wz>": one of RGPU_HELM_NAMES (m, v, w, b), then the three integer weights, none of them zero.  Each
+  // sample of each spec is one file <outputDir>/<outputPrefix>_helmholtz<m>_<step, 7 digits>.npy -- '<f8', C order, shape (3, S): the
+  // solenoidal power, the compressive power, then the modes of each shell -- and one line "step t spectrum spec file" of
+  // <outputPrefix>_helmholtz.txt.  A batch serves one consumer: the Helmholtz spectra take the batches where none of the maps, the
+  // PDFs and the spectra does, ahead of the monitor.  Not for z-slab, hooked or 2D runs, nor for a box with an extent that is no
+  // power of two in 4 .. 1024: noted once, the run goes on.
+  const bool helmEnabled = cfg_.get_bool("helmholtz", "enabled", false);
+  const int helm_every = helmEnabled ? (int)cfg_.get_integer("helmholtz", "every", 10) : 0;
+  if (helmEnabled && helm_every < 1) throw std::runtime_error("[helmholtz] every must be at least 1");
+  bool noted_helm = false;
+  if (helmEnabled && !spectra_box)
+    note_once(&noted_helm, p_.nz_global == 1 ? "2D run: the Helmholtz spectrum files are not written" : (slab() || hooked_) ? "z-slab run: the Helmholtz spectrum files are not written"
+                                                                                                      : "an extent of the box is not a power of two in 4 .. 1024: the Helmholtz spectrum files are not written");
+  std::vector<rgpu_helm_spec> helm_specs;
+  std::vector<std::string> helm_texts;
+  std::vector<size_t> helm_at(1, 0);   // spec m of a sample begins at helm_at[m]; helm_at.back(): the doubles of a sample
+  if (helmEnabled && spectra_box) {
+    for (int m = 0; m < RGPU_HELM_MAX; ++m) {
+      const std::string key = "spectrum" + std::to_string(m);
+      std::string text = cfg_.get_string("helmholtz", key, "");
+      if (text.empty()) break;
+      if (text.size() >= 2 && text.front() == '"' && text.back() == '"') text = text.substr(1, text.size() - 2);
+      std::istringstream in(text);
+      std::string field, rest, name;
+      rgpu_helm_spec sp = {};
+      bool ok = static_cast<bool>(in >> field >> sp.wx >> sp.wy >> sp.wz) && !(in >> rest);
+      std::istringstream names(RGPU_HELM_NAMES);
+      sp.field = -1;
+      for (int q = 0; names >> name; ++q)
+        if (name == field) sp.field = q;
+      ok = ok && sp.field >= 0;
+      const int shells = ok ? rgpu_helm_shells(ctx_, &sp) : 0;
+      if (shells == 0)
+        throw std::runtime_error("[helmholtz] " + key + "=" + text + ": expected \"<field> <wx> <wy> <wz>\" (a field of \"" RGPU_HELM_NAMES "\"; weights 1 .. " +
+                                 std::to_string(RGPU_SPECTRUM_MAX_WEIGHT) + "; at most " + std::to_string(RGPU_SPECTRUM_MAX_SHELLS) + " shells)");
+      helm_specs.push_back(sp);
+      std::string word = text;   // (one word in the list: the blanks become colons)
+      for (char& ch : word) if (ch == ' ' || ch == '\t') ch = ':';
+      helm_texts.push_back(word);
+      helm_at.push_back(helm_at.back() + 3 * (size_t)shells);
+    }
+  }
+  const bool helm_on = !helm_specs.empty();
+  const std::string helm_list = rs_.outputDir + "/" + rs_.outputPrefix + "_helmholtz.txt";
+  // n samples of all Helmholtz spectra: the .npy files and their lines in the list
+  const auto helm_files = [&](int n, const int* step, const double* t, const double* v) {
+    std::ofstream list(helm_list.c_str(), std::ios::app);
+    if (!list) throw std::runtime_error("cannot write " + helm_list);
+    char num[64];
+    for (int k = 0; k < n; ++k)
+      for (size_t m = 0; m < helm_specs.size(); ++m) {
+        std::snprintf(num, sizeof(num), "_helmholtz%d_%07d.npy", (int)m, step[k]);
+        const std::string name = rs_.outputPrefix + num, path = rs_.outputDir + "/" + name;
+        const size_t doubles = helm_at[m + 1] - helm_at[m];
+        // NumPy format 1.0, as the maps' files: the header padded with spaces to a multiple of 64
+        std::string head = "{'descr': '<f8', 'fortran_order': False, 'shape': (3, " + std::to_string(doubles / 3) + "), }";
+        head.append(63 - (10 + head.size()) % 64, ' ');
+        head += "\n";
+        std::ofstream f(path.c_str(), std::ios::binary | std::ios::trunc);
+        const char magic[10] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0, (char)(head.size() & 0xff), (char)(head.size() >> 8)};
+        f.write(magic, 10);
+        f.write(head.data(), (std::streamsize)head.size());
+        f.write(reinterpret_cast<const char*>(v + (size_t)k * helm_at.back() + helm_at[m]), (std::streamsize)(doubles * sizeof(double)));
+        if (!f) throw std::runtime_error("cannot write " + path);
+        std::snprintf(num, sizeof(num), " %.17g", t[k]);
+        list << step[k] << num << " " << m << " " << helm_texts[m] << " " << name << "\n";
+      }
+  };
+  std::vector<double> helm_v, helm_t;
+  std::vector<int> helm_step;
+  const auto helm_direct = [&](int n) {   // the Helmholtz spectra of the current state U[n % 2]
+    helm_v.resize(std::max(helm_v.size(), helm_at.back()));
+    check(rgpu_state_helm_spectra(ctx_, n % 2, (int)helm_specs.size(), helm_specs.data(), helm_v.data()), "state_helm_spectra");
+    helm_files(1, &n, &totalTime_, helm_v.data());
+  };
+  if (helm_on && !(totalTime_ > 0)) {   // the start of a run
+    std::ofstream f(helm_list.c_str(), std::ios::trunc);
+    if (!f) throw std::runtime_error("cannot write " + helm_list);
+    f << "# nStep totalTime spectrum spec file\n";
+  }
   const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   while (totalTime_ < rs_.tEnd && nStep < rs_.nStepmax) {
     if (rs_.nLog > 0 && (nStep % rs_.nLog) == 0 && p_.slab_rank == 0)
@@ -1105,13 +1187,23 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     const bool maps_batched = maps_on && !historyEnabled && quiet > 1;
     const bool pdfs_batched = pdfs_on && !historyEnabled && quiet > 1 && !maps_batched;
     const bool spectra_batched = spectra_on && !historyEnabled && quiet > 1 && !maps_batched && !pdfs_batched;
-    const bool monitor_batched = monitor_on && !historyEnabled && quiet > 1 && !maps_batched && !pdfs_batched && !spectra_batched;
+    const bool helm_batched = helm_on && !historyEnabled && quiet > 1 && !maps_batched && !pdfs_batched && !spectra_batched;
+    const bool monitor_batched = monitor_on && !historyEnabled && quiet > 1 && !maps_batched && !pdfs_batched && !spectra_batched && !helm_batched;
     if (monitor_on && !monitor_batched && mon_every - nStep % mon_every < quiet) quiet = mon_every - nStep % mon_every;   // the direct call follows
     if (maps_on && !maps_batched && maps_every - nStep % maps_every < quiet) quiet = maps_every - nStep % maps_every;      // the direct call follows
     if (pdfs_on && !pdfs_batched && pdfs_every - nStep % pdfs_every < quiet) quiet = pdfs_every - nStep % pdfs_every;      // the direct call follows
     if (spectra_on && !spectra_batched && spectra_every - nStep % spectra_every < quiet) quiet = spectra_every - nStep % spectra_every;   // the direct call follows
+    if (helm_on && !helm_batched && helm_every - nStep % helm_every < quiet) quiet = helm_every - nStep % helm_every;   // the direct call follows
     const int nStep_before = nStep;
-    if (spectra_batched) {
+    if (helm_batched) {
+      int mn = 0;
+      const size_t cap = (size_t)(quiet / helm_every + 1);
+      if (helm_step.size() < cap) { helm_step.resize(cap); helm_t.resize(cap); }
+      if (helm_v.size() < cap * helm_at.back()) helm_v.resize(cap * helm_at.back());
+      const int rc = rgpu_run_steps_helm_spectra(ctx_, quiet, rs_.tEnd, &nStep, &totalTime_, &dt, 0, helm_every, (int)helm_specs.size(), helm_specs.data(), &mn, helm_step.data(), helm_t.data(), helm_v.data());
+      helm_files(mn, helm_step.data(), helm_t.data(), helm_v.data());
+      if (rc < 0) check(rc, "run_steps_helm_spectra");
+    } else if (spectra_batched) {
       int mn = 0;
       const size_t cap = (size_t)(quiet / spectra_every + 1);
       if (spectra_step.size() < cap) { spectra_step.resize(cap); spectra_t.resize(cap); }
@@ -1172,6 +1264,7 @@ int GodunovRun::start(double* mcell_per_s, rgpuh_attach_fn attach, void* user) {
     if (maps_on && !maps_batched && nStep > nStep_before && nStep % maps_every == 0) maps_direct(nStep);
     if (pdfs_on && !pdfs_batched && nStep > nStep_before && nStep % pdfs_every == 0) pdfs_direct(nStep);
     if (spectra_on && !spectra_batched && nStep > nStep_before && nStep % spectra_every == 0) spectra_direct(nStep);
+    if (helm_on && !helm_batched && nStep > nStep_before && nStep % helm_every == 0) helm_direct(nStep);
   }
   check(rgpu_synchronize(ctx_), "synchronize");
   if (hooked_) hook_check(hooks_.barrier(hooks_.self), "barrier");

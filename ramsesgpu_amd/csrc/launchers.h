@@ -12,6 +12,7 @@
 #include "kernels_monitor_maps.h"     // the map monitor: twelve channels per pixel, slices and sums along an axis, on the same terms
 #include "kernels_monitor_pdf.h"      // the PDF monitor: counts per class of thirteen channels, 1D and joint, on the same terms
 #include "kernels_monitor_spectrum.h" // the spectrum monitor: shell-binned power of thirteen channels, line transforms in three passes
+#include "kernels_monitor_helm.h"     // the Helmholtz spectra: the spectrum monitor's transforms per component, projected mode by mode
 #include "rg_options.h"        // option spec (hydro_pick_spec)
 #include "step_clock_rec.h"   // StepClock: the time step as a device record (kernels with a `clk` member read it instead of their by-value arguments)
 

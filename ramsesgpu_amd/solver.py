@@ -46,6 +46,21 @@ def spectrum_spec(spec):
     return _capi.RgpuSpectrumSpec(mask, wx, wy, wz)
 
 
+# the series out of run_steps_helm_spectra: step numbers [n], times [n], and per spec the solenoidal power, the compressive power and
+# the mode counts, each [n, S]
+HelmSeries = collections.namedtuple("HelmSeries", "step t solenoidal compressive modes")
+
+
+def helm_spec(spec):
+    """a spec of a Helmholtz spectrum as _capi.RgpuHelmSpec, from one, or from (field, (wx, wy, wz)) -- the field one of
+    _capi.HELM_NAMES ("m", "v", "w", "b") or its index"""
+    if isinstance(spec, _capi.RgpuHelmSpec):
+        return spec
+    field, weights = spec
+    wx, wy, wz = (int(w) for w in weights)
+    return _capi.RgpuHelmSpec(field if isinstance(field, int) else _capi.HELM_NAMES.index(field), wx, wy, wz)
+
+
 def spectrum_shells(shape, weights):
     """(S, M) of the weights (wx, wy, wz) on a box of shape (nx, ny, nz), from the integer rule of include/rgpu.h ("spectrum monitors")
     without a context: the number of shells and the modes of each, numpy.int64 [S].  Shell s holds the q = (wx kx)^2 + (wy ky)^2 +
@@ -519,6 +534,46 @@ class Solver:
             self._chk(done, "run_steps_spectra")
         self.dt_log = [log[i] for i in range(done)]
         return done, self.spectrum_series
+
+    def _helm_specs(self, specs):
+        """specs as helm_spec takes them -> (the C array, the shells of each on this context; 0 where the library refuses it)"""
+        arr = (_capi.RgpuHelmSpec * max(len(specs), 1))()
+        for m, spec in enumerate(specs):
+            arr[m] = helm_spec(spec)
+        return arr, [int(self.lib.rgpu_helm_shells(self.ctx, C.byref(arr[m]))) for m in range(len(specs))]
+
+    def state_helm_spectra(self, specs, parity=None):
+        """Helmholtz spectra of U[parity] (default: nStep % 2) of a 3D state whose extents are powers of two, the box taken as periodic:
+        a list, per spec, of (Psol, Pcomp, M) -- the solenoidal power, the compressive power and the number of modes of each shell,
+        numpy.float64 [S] (rgpu_state_helm_spectra; include/rgpu.h, "Helmholtz spectra").  A spec is (field, (wx, wy, wz)), see helm_spec"""
+        arr, shells = self._helm_specs(specs)
+        out = np.zeros(max(3 * sum(shells), 1))
+        par = self.nStep % 2 if parity is None else int(parity)
+        self._chk(self.lib.rgpu_state_helm_spectra(self.ctx, par, len(specs), arr, out.ctypes.data_as(_capi.c_double_p)), "state_helm_spectra")
+        cuts = np.cumsum([0] + [3 * s for s in shells])
+        return [tuple(out[cuts[m] + i * shells[m]:cuts[m] + (i + 1) * shells[m]].copy() for i in range(3)) for m in range(len(specs))]
+
+    def run_steps_helm_spectra(self, nsteps, every, specs, tEnd=float("inf")):
+        """run_steps with a sample of the Helmholtz spectra `specs` after every step that brings nStep to a multiple of `every`
+        (rgpu_run_steps_helm_spectra: inside the device-clock batches the transforms run on the device, one read-back per batch).
+        Returns (done, HelmSeries): the steps done and the samples of this call -- .step [n], .t [n] (the time after that step),
+        .solenoidal, .compressive and .modes lists per spec of numpy.float64 [n, S]"""
+        arr, shells = self._helm_specs(specs)
+        cap = max(int(nsteps), 0) // max(int(every), 1) + 1
+        n, t, d, mn = C.c_int(self.nStep), C.c_double(self.totalTime), C.c_double(self.dt), C.c_int(0)
+        log = (C.c_double * max(int(nsteps), 1))()
+        mstep, mt, mv = np.zeros(cap, dtype=np.intc), np.zeros(cap), np.zeros((cap, max(3 * sum(shells), 1)))
+        done = self.lib.rgpu_run_steps_helm_spectra(self.ctx, int(nsteps), float(tEnd), C.byref(n), C.byref(t), C.byref(d), log, int(every), len(specs), arr, C.byref(mn),
+                                                    mstep.ctypes.data_as(C.POINTER(C.c_int)), mt.ctypes.data_as(_capi.c_double_p), mv.ctypes.data_as(_capi.c_double_p))
+        k = mn.value
+        self.nStep, self.totalTime, self.dt = n.value, t.value, d.value   # (they describe the steps that ran, also when the call failed)
+        cuts = np.cumsum([0] + [3 * s for s in shells])
+        part = lambda i: [mv[:k, cuts[m] + i * shells[m]:cuts[m] + (i + 1) * shells[m]].copy() for m in range(len(specs))]
+        self.helm_series = HelmSeries(mstep[:k].astype(int), mt[:k].copy(), part(0), part(1), part(2))
+        if done < 0:
+            self._chk(done, "run_steps_helm_spectra")
+        self.dt_log = [log[i] for i in range(done)]
+        return done, self.helm_series
 
     def history_turbulence(self, nStep=None):
         """history_turbulence (MHDRunBase.cpp:3626-3810) reduced on the device: the 18 columns after totalTime and dt"""
